@@ -4,7 +4,9 @@
 Workload (BASELINE.json metric): separable bounded quadratic, n = 1e8, m = 10, fp64,
 l = -1, u = +1, x0 = 0, factr = pgtol = 0, on-device objective.  A "step"
 is one L-BFGS-B iteration (one NEW_X return): every kernel of the hot path runs, plus the
-f/g evaluations the line search asks for.  With --gpus N the n rows are sharded over N
+f/g evaluations the line search asks for.  Every timed step runs with the memory full (col == m); the problem
+converges after a fixed number of iterations, so for a large K new runs of it start from x0 (warmed up again
+outside the clock) until K steps are timed.  With --gpus N the n rows are sharded over N
 ranks (STRONG scaling: n stays 1e8) and every reduction is completed with ONE RCCL collective
 per host sync (all-gather of the <= 8m+15 partials, reduced in rank order on every rank).
 
@@ -35,6 +37,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 achievable
+# --dump-outputs: rows of x and g written (x, g and the row numbers as fp64: 48 MB, under the 64 MB a dump may take)
+DUMP_ROWS = 1 << 21
+DUMP_SEED = 20260
 
 
 def parse():
@@ -81,7 +86,14 @@ def parse():
                          "(N=1 only; skipped by itself when this process already runs under a profiler)")
     ap.add_argument("--pmc-child", action="store_true",
                     help="(internal) the run rocprofv3 counts: warm-up + timed iterations, then exit")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the caller received at the last one to DIR/<name>.npy: "
+                         "x.npy, g.npy (a fixed, seeded sample of %d rows when n is larger; the row numbers in "
+                         "sample_rows.npy), f.npy, isave.npy and dsave.npy (its wall-clock slots zeroed)" % DUMP_ROWS)
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 class stdout_to_stderr:
@@ -370,6 +382,13 @@ def parity_in_run(rows, n, m, real32, kind):
     return out
 
 
+X0 = {0: 0.0, 1: 3.0}   # starting point of each objective kind (every row the same)
+
+
+class RunEnded(RuntimeError):
+    """the solver ended the run by itself (CONVERGENCE / ABNORMAL_TERMINATION): a new run of the problem may start"""
+
+
 def problem_tensors(torch, dev, kind, n_loc, row0, real32, arbitrary_box=False):
     """x0, l, u, nbd of this rank's rows: kind 0 = separable bounded quadratic,
     kind 1 = extended Rosenbrock with the drivers' box (test/driver1.f90:233-251).
@@ -378,7 +397,7 @@ def problem_tensors(torch, dev, kind, n_loc, row0, real32, arbitrary_box=False):
     the passes stream l, u and nbd: what a caller with per-variable bounds gets."""
     rdt = torch.float32 if real32 else torch.float64
     if kind == 0:
-        x = torch.zeros(n_loc, dtype=rdt, device=dev)
+        x = torch.full((n_loc,), X0[0], dtype=rdt, device=dev)
         l = torch.full_like(x, -1.0)
         u = torch.full_like(x, 1.0)
         if arbitrary_box:
@@ -387,7 +406,7 @@ def problem_tensors(torch, dev, kind, n_loc, row0, real32, arbitrary_box=False):
             u += ((104729 * i) % 1000033).to(rdt) * 1.0e-9
             del i
     else:
-        x = torch.full((n_loc,), 3.0, dtype=rdt, device=dev)
+        x = torch.full((n_loc,), X0[1], dtype=rdt, device=dev)
         u = torch.full_like(x, 100.0)
         l = torch.full_like(x, -100.0)
         l[(row0 % 2)::2] = 1.0          # odd 1-based global index
@@ -405,7 +424,7 @@ class Run:
         dev = torch.device("cuda", local_rank)
         self.dev = dev
         row0, n_loc = la.block_partition(n, world, rank)
-        self.n_loc = n_loc
+        self.row0, self.n_loc = row0, n_loc
         # torch_objective: f, g by torch ops on torch's current stream, ordered against the solver's stream with events
         # in both directions (stream_ordered: lbfgsb_hip_return_event / lbfgsb_hip_wait_stream), f handed over as a
         # device scalar (lbfgsb_hip_f_device) -- what an ordinary PyTorch caller does, with no host sync of its own
@@ -504,8 +523,17 @@ class Run:
                 isv = sol.isave
                 self.rows.append((int(isv[29]), int(isv[33]), int(isv[32]), int(isv[37]), float(sol.f[0])))
                 self.stamps.append(time.perf_counter())
+            elif task.startswith(("CONVERGENCE", "ABNORMAL_TERMINATION")):
+                raise RunEnded("solver stopped: " + task)
             else:
                 raise RuntimeError("solver stopped: " + task)
+
+    def restart(self):
+        """a new run of the same problem from x0 (task START), as a caller starts one after the solver stopped"""
+        self.xs[0].fill_(X0[self.kind])
+        self.gs[0].zero_()
+        self.cur = 0
+        self.sol.set_task("START")
 
     def close(self):
         import gc
@@ -518,21 +546,24 @@ class Run:
         self.torch.cuda.empty_cache()
 
 
-def timed_leg(run, steps, warm_min, need_full_memory=True):
-    """first iteration apart, then untimed until the memory is full (col == m) and at least
-    warm_min iterations have run, then `steps` timed iterations bracketed by barriers."""
+def warm_up(run, done, warm_min, need_full_memory=True):
+    """untimed iterations until the memory is full (col == m) and at least warm_min iterations have run (`done` of
+    them already have), then the packing iteration of option compact_w.  A run that ends on the way is started
+    again.  -> iterations run in all"""
     sol, m = run.sol, run.m
-    run.barrier()
-    tw0 = time.perf_counter()
-    run.advance(1)
-    run.barrier()
-    first_iter_s = time.perf_counter() - tw0
-    nseg_first = int(sol.isave[32])
-    warm_done = 1
-    while warm_done < warm_min or (need_full_memory and int(sol.isave[27]) < m):
-        run.advance(1)
-        warm_done += 1
-        if warm_done > warm_min + 4 * m + 20:
+    since = done                 # iterations of the current run
+    packs0 = sol.compact_stats()[0]   # (the context's count of packs: a new run's packing adds one)
+    while done < warm_min or (need_full_memory and int(sol.isave[27]) < m):
+        try:
+            run.advance(1)
+        except RunEnded:
+            run.restart()
+            since = 0
+            packs0 = sol.compact_stats()[0]
+            continue
+        done += 1
+        since += 1
+        if since > warm_min + 4 * m + 20:
             raise RuntimeError("col never reached m = %d (skipped updates?)" % m)
     # option compact_w: the layout is packed in the first iteration with the memory full and a settled free set (a
     # one-off re-sort of all of W): that iteration belongs to the warm-up, not to the timed region
@@ -540,44 +571,129 @@ def timed_leg(run, steps, warm_min, need_full_memory=True):
     while extra < 6:
         packs, _unpacks, packed, eligible = sol.compact_stats()
         nf = int(sol.isave[37])
-        if not eligible or packed or nf > 0.9 * run.n or packs > 0:
+        if not eligible or packed or nf > 0.9 * run.n or packs > packs0:
             break
         run.advance(1)
-        warm_done += 1
+        done += 1
         extra += 1
+    return done
+
+
+def timed_leg(run, steps, warm_min, need_full_memory=True):
+    """first iteration apart, then untimed until the memory is full (col == m) and at least
+    warm_min iterations have run, then `steps` timed iterations bracketed by barriers.
+    The problem converges after a fixed number of iterations: when the solver ends the run inside the timed
+    region, the timed segment ends at the last NEW_X return, a new run of the problem starts from x0 and warms up
+    as above outside the clock, and the next segment goes on -- `steps` iterations are timed, all with col == m.
+    dt, setulb time, the counters and the pass clocks are summed over the segments (those of a segment that ended
+    with its run include the call that ended it)."""
+    sol = run.sol
     run.barrier()
-    ts0, st0 = run.t_setulb, sol.stats()
-    hg0 = sol.host_gap()
-    hs0 = sol.host_segments()
-    sol.pass_clock(1)            # hipEvents around every launch of the three W passes
+    tw0 = time.perf_counter()
+    run.advance(1)
+    run.barrier()
+    first_iter_s = time.perf_counter() - tw0
+    nseg_first = int(sol.isave[32])
+    warm_done = warm_up(run, 1, warm_min, need_full_memory)
+    names = ("linesearch_and_return", "caller_new_x_to_reentry", "termination_matupd_formt", "cauchy_freev",
+             "formk_closed_form_solves")
+    acc = dict(t=0.0, st={}, hg=[0.0, 0], hs=[0.0] * len(names), clk={})
+
+    def segment_start():
+        run.barrier()
+        sol.pass_clock(1)            # hipEvents around every launch of the three W passes (reset and start)
+        return run.t_setulb, sol.stats(), sol.host_gap(), sol.host_segments()
+
+    def segment_end(mark):
+        ts0, st0, hg0, hs0 = mark
+        for nm, (ms, cnt) in sol.pass_clock(0).items():
+            ms_, cnt_ = acc["clk"].get(nm, (0.0, 0))
+            acc["clk"][nm] = (ms_ + ms, cnt_ + cnt)
+        st1, hg1, hs1 = sol.stats(), sol.host_gap(), sol.host_segments()
+        acc["t"] += run.t_setulb - ts0
+        for k, v in st1.items():
+            acc["st"][k] = acc["st"].get(k, 0) + (v - st0[k])
+        acc["hg"] = [acc["hg"][0] + hg1[0] - hg0[0], acc["hg"][1] + hg1[1] - hg0[1]]
+        acc["hs"] = [a_ + b - c for a_, b, c in zip(acc["hs"], hs1, hs0)]
+        return st1
+
     cols_timed, step_ms = [], []
+    dt, restarts, seg_steps = 0.0, 0, 0
+    mark = segment_start()
     t0 = time.perf_counter()
     tp = t0
-    for _ in range(steps):
-        run.advance(1)
+    while len(cols_timed) < steps:
+        try:
+            run.advance(1)
+        except RunEnded:
+            if seg_steps == 0 and restarts:
+                raise RuntimeError("a new run ended before its first timed iteration")
+            # (the call that ended the run is not a timed step: the segment ends at its last NEW_X return)
+            dt += tp - t0
+            segment_end(mark)
+            run.restart()
+            warm_done += warm_up(run, 0, warm_min, need_full_memory)
+            restarts += 1
+            seg_steps = 0
+            mark = segment_start()
+            t0 = time.perf_counter()
+            tp = t0
+            continue
         cols_timed.append(int(sol.isave[27]))
+        seg_steps += 1
         tn = time.perf_counter()      # (host clock at the NEW_X return: no extra sync, the value is K / dt)
         step_ms.append((tn - tp) * 1e3)
         tp = tn
     run.barrier()
-    dt = time.perf_counter() - t0
-    clocks = sol.pass_clock(0)   # {pass: (ms_total, launches)} over the timed region
-    dt_setulb = run.t_setulb - ts0
+    dt += time.perf_counter() - t0
+    st1 = segment_end(mark)
+    clocks = acc["clk"]          # {pass: (ms_total, launches)} over the timed region
+    dt_setulb = acc["t"]
+    st0 = {k: st1[k] - acc["st"][k] for k in st1}
     dt_min = dt
     if run.world > 1:
         tt = run.torch.tensor([dt, dt_setulb, -dt], dtype=run.torch.float64, device=run.dev)
         run.dist.all_reduce(tt, op=run.dist.ReduceOp.MAX)
         dt, dt_setulb, dt_min = float(tt[0]), float(tt[1]), -float(tt[2])
-    st1 = sol.stats()
-    hg1 = sol.host_gap()
-    st1["host_gap_us"] = (hg1[0] - hg0[0]) / max(1, hg1[1] - hg0[1]) * 1e6
-    hs1 = sol.host_segments()
-    names = ("linesearch_and_return", "caller_new_x_to_reentry", "termination_matupd_formt", "cauchy_freev",
-             "formk_closed_form_solves")
-    st1["host_segments_us"] = {nm: (b - a_) / max(1, hg1[1] - hg0[1]) * 1e6 for nm, a_, b in zip(names, hs0, hs1)}
+    gaps = max(1, acc["hg"][1])
+    st1["host_gap_us"] = acc["hg"][0] / gaps * 1e6
+    st1["host_segments_us"] = {nm: v / gaps * 1e6 for nm, v in zip(names, acc["hs"])}
     return dict(first_iter_s=first_iter_s, nseg_first=nseg_first, warm_done=warm_done, cols_timed=cols_timed,
-                dt=dt, dt_min=dt_min, dt_setulb=dt_setulb, clocks=clocks, st0=st0, st1=st1,
+                dt=dt, dt_min=dt_min, dt_setulb=dt_setulb, clocks=clocks, st0=st0, st1=st1, restarts=restarts,
                 step_ms_median=float(np.median(step_ms)), step_ms_max=float(np.max(step_ms)))
+
+
+def dump_outputs(run, rank, out_dir):
+    """--dump-outputs: what the caller holds at the NEW_X return of the last timed step -- x, g (all rows, or
+    DUMP_ROWS rows drawn once per stratum of n / DUMP_ROWS rows with a fixed seed, so that two runs with the same
+    arguments write the same rows), f, isave, dsave -- as out_dir/<name>.npy.  Every rank takes part (the sampled
+    rows of the other ranks arrive by one sum over the ranks); rank 0 writes."""
+    torch, n, sol = run.torch, run.n, run.sol
+    if n <= DUMP_ROWS:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        edges = np.arange(DUMP_ROWS + 1, dtype=np.int64) * n // DUMP_ROWS
+        rows = np.random.default_rng(DUMP_SEED).integers(edges[:-1], edges[1:])
+    mine = (rows >= run.row0) & (rows < run.row0 + run.n_loc)
+    at = torch.from_numpy(np.nonzero(mine)[0]).to(run.dev)
+    local = torch.from_numpy(rows[mine] - run.row0).to(run.dev)
+    vals = {}
+    for name, v in (("x", run.x), ("g", run.g)):
+        full = torch.zeros(len(rows), dtype=v.dtype, device=run.dev)
+        full[at] = v[local]
+        if run.world > 1:
+            run.dist.all_reduce(full)        # (each row is nonzero on one rank only)
+        vals[name] = full.cpu().numpy()
+    if rank != 0:
+        return
+    dsave = sol.dsave.astype(np.float64)
+    dsave[5:10] = 0.0                        # cpu1, cachyt, sbtime, lnscht, time1: wall clock
+    vals.update(f=np.array([sol.f[0]], dtype=np.float64), isave=sol.isave.astype(np.float64), dsave=dsave,
+                sample_rows=rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in vals.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    sys.stderr.write("bench.py: %s written to %s\n" % (", ".join(sorted(vals)), out_dir))
 
 
 def pass_bytes(col, rbytes, pp, lean=True, ub=0, wfrac=1.0):
@@ -730,7 +846,7 @@ def compact_line(out):
         "compact_w": c.get("compact_w"),
         "parity_in_run": {k: par.get(k) for k in ("rows_checked", "ok", "iters", "f_rel_tol")},
         "rccl_nranks": c["rccl_nranks"], "first_iteration_s": c["first_iteration_s"],
-        "time_to_30_iterations_s": c.get("time_to_30_iterations_s"),
+        "time_to_30_iterations_s": c.get("time_to_30_iterations_s"), "runs_restarted": c.get("runs_restarted"),
     }
     if out["n_gpus"] > 1:   # what a scaling run needs to explain itself
         line["config"].update({
@@ -832,6 +948,8 @@ def main():
     r = timed_leg(run, a.steps, max(a.warmup, m + 1), need_full_memory=not a.rosenbrock)
     cols_timed, clocks, dt, dt_setulb = r["cols_timed"], r["clocks"], r["dt"], r["dt_setulb"]
     assert a.rosenbrock or min(cols_timed) == max(cols_timed) == m, cols_timed
+    if a.dump_outputs:
+        dump_outputs(run, rank, a.dump_outputs)
     if a.pmc_child:   # (the run live_traffic() counts: nothing but the iterations themselves)
         run.close()
         print(json.dumps({"pmc_child": True, "steps": a.steps, "ms_per_step": dt / a.steps * 1e3}))
@@ -852,6 +970,7 @@ def main():
     for (it, *_), ts in zip(run.rows, run.stamps):
         if it == 30:
             tts30 = ts - run.t_start
+            break
     first_per_rank = [r["first_iter_s"]]
     if world > 1:
         ft = torch.tensor([r["first_iter_s"]], dtype=torch.float64, device=run.dev)
@@ -1017,6 +1136,8 @@ def main():
                    "refresh_count": stats["refreshes"],
                    "time_to_30_iterations_s": tts30,
                    "iterations_run": run.rows[-1][0] if run.rows else 0,
+                   # runs of the problem started again inside the timed region (its run converged before `steps`)
+                   "runs_restarted": r["restarts"],
                    "defer_lnsrch": not a.no_defer,
                    # option compact_w: the passes over W on the tile-local free-row layout -- [on, tile re-sorts,
                    # un-sorts, packed at the end, fraction of the rows whose W entries a pass needs (nfree / n)]

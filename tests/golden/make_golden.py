@@ -16,7 +16,10 @@ Files
   <name>_traj.npz   per setulb return k: task, f, x, g, isave, dsave, lsave
   <name>_state.npz  full caller state (wa, iwa, csave too) at selected returns;
                     consecutive pairs (k, k+1) allow one-step parity tests.
-  ref_outputs/      the reference's own golden transcripts (test/OUTPUTS/*).
+  ref_outputs/      the reference's own golden transcripts (test/OUTPUTS/*), and what it printed
+                    at iprint >= 99 and on random problems (transcripts()).
+  live_ref_state_digests.json  sha256 of every state array after every return on two
+                    problems outside the fixtures (state_digests()).
 """
 import os
 import shutil
@@ -62,6 +65,22 @@ def transcripts():
         with open(path, "w") as fh:
             fh.write(out)
         print("wrote", path, len(out.splitlines()), "lines")
+    # random problems of tests/test_gpu_fuzz.py: stdout and the iteration file of each run
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_fortran_drivers import LIVE_CASES, live_case_name
+    for spec, ipr in LIVE_CASES:
+        with tempfile.TemporaryDirectory() as cwd:
+            out = subprocess.run([sys.executable, worker, "ref", spec, "0", "0", str(ipr), "25"], cwd=cwd,
+                                 capture_output=True, text=True, check=True).stdout
+            itf = os.path.join(cwd, "iterate.dat")
+            itf = open(itf).read() if os.path.exists(itf) else ""
+        stem = os.path.join(OUT, "ref_outputs", live_case_name(spec, ipr))
+        with open(stem + ".txt", "w") as fh:
+            fh.write(out)
+        with open(stem + "_iterate.txt", "w") as fh:
+            fh.write(itf)
+        print("wrote", stem, len(out.splitlines()), "+", len(itf.splitlines()), "lines")
 
 
 def record(kind, name, p, full_calls, on_new_x=None, max_calls=10**9, lite_xg=None):
@@ -99,6 +118,17 @@ def record(kind, name, p, full_calls, on_new_x=None, max_calls=10**9, lite_xg=No
         name, len(traj["f"]), s.isave[29], s.task_s, float(s.f[0])))
 
 
+def state_digests():
+    """tests/test_oracle_golden.py's problems outside the fixtures: digests of the reference's state arrays"""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_oracle_golden as tg
+    d = {name: tg.state_digests(po, "ref", mk(po)) for name, mk in tg.LIVE_PROBLEMS.items()}
+    with open(tg.LIVE_DIGESTS, "w") as fh:
+        json.dump(d, fh, indent=0)
+    print("wrote", tg.LIVE_DIGESTS, {k: len(v) for k, v in d.items()})
+
+
 def main():
     # (i) driver1: n=25 m=5 factr=1e7 pgtol=1e-5, everything at every return
     record("ref", "driver1", po.problem_rosenbrock(25, 5, 1e7, 1e-5), "all")
@@ -131,6 +161,9 @@ def main():
 if __name__ == "__main__":
     if sys.argv[1:] == ["transcripts"]:
         transcripts()
+    elif sys.argv[1:] == ["digests"]:
+        state_digests()
     else:
         main()
         transcripts()
+        state_digests()

@@ -2,19 +2,17 @@
 the way RCCL fails, or the 8-rank path's only safety net cannot see a regression:
   * a collective returns BEFORE its data have moved (asynchronous on the caller's stream);
   * ranks that pass different counts are caught: the result is poisoned, the next call is refused.
-Two rank threads of this process, one GPU, the stand-in driven directly through ctypes."""
+Two rank processes, one GPU, the stand-in driven directly through ctypes."""
 import ctypes as C
 import json
 import os
 import subprocess
 import sys
-import threading
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 class UniqueId(C.Structure):
@@ -22,7 +20,11 @@ class UniqueId(C.Structure):
 
 
 def _lib():
-    lib = C.CDLL(os.environ["LBFGSB_FAKE_RCCL_SO"])
+    return _lib_at(os.environ["LBFGSB_FAKE_RCCL_SO"])
+
+
+def _lib_at(so):
+    lib = C.CDLL(so)
     lib.ncclGetUniqueId.argtypes = [C.POINTER(UniqueId)]
     lib.ncclCommInitRank.argtypes = [C.POINTER(C.c_void_p), C.c_int, UniqueId, C.c_int]
     lib.ncclAllGather.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
@@ -35,37 +37,21 @@ def _lib():
 NCCL_DOUBLE = 8   # ncclFloat64 (rccl.h)
 
 
-def _two_ranks(body):
-    """run body(rank, comm, lib, stream, torch) on two threads with a 2-rank communicator each"""
+def _one_rank(body, rank, uid_hex):
+    """run body(rank, comm, lib, stream, torch) as one rank of a 2-rank communicator; (result, rc of destroy)"""
     import torch
     lib = _lib()
-    uid = UniqueId()
-    assert lib.ncclGetUniqueId(C.byref(uid)) == 0
-    out, errs = [None, None], []
-
-    def worker(rank):
-        try:
-            torch.cuda.set_device(0)
-            comm = C.c_void_p()
-            assert lib.ncclCommInitRank(C.byref(comm), 2, uid, rank) == 0
-            n, r = C.c_int(), C.c_int()
-            assert lib.ncclCommCount(comm, C.byref(n)) == 0 and lib.ncclCommUserRank(comm, C.byref(r)) == 0
-            assert (n.value, r.value) == (2, rank)
-            stream = torch.cuda.Stream()
-            out[rank] = body(rank, comm, lib, stream, torch)
-            stream.synchronize()
-            out[rank] = (out[rank], lib.ncclCommDestroy(comm))
-        except BaseException as e:   # noqa: BLE001
-            errs.append(e)
-    ts = [threading.Thread(target=worker, args=(k,)) for k in range(2)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(120)
-    assert not any(t.is_alive() for t in ts), "a rank thread hangs"
-    if errs:
-        raise errs[0]
-    return out
+    uid = UniqueId.from_buffer_copy(bytes.fromhex(uid_hex))
+    torch.cuda.set_device(0)
+    comm = C.c_void_p()
+    assert lib.ncclCommInitRank(C.byref(comm), 2, uid, rank) == 0
+    n, r = C.c_int(), C.c_int()
+    assert lib.ncclCommCount(comm, C.byref(n)) == 0 and lib.ncclCommUserRank(comm, C.byref(r)) == 0
+    assert (n.value, r.value) == (2, rank)
+    stream = torch.cuda.Stream()
+    res = body(rank, comm, lib, stream, torch)
+    stream.synchronize()
+    return res, lib.ncclCommDestroy(comm)
 
 
 def scenario_async():
@@ -88,7 +74,7 @@ def scenario_async():
         got = recv.cpu().numpy()
         assert np.all(got[:k] == 1.0) and np.all(got[k:] == 2.0)
         return bool(returned_before_done)
-    return _two_ranks(body)
+    return body
 
 
 def scenario_mismatch():
@@ -103,19 +89,32 @@ def scenario_mismatch():
         rc2 = lib.ncclAllGather(send.data_ptr(), recv.data_ptr(), 64, NCCL_DOUBLE, comm,
                                 C.c_void_p(stream.cuda_stream))
         return rc1, poisoned, rc2
-    return _two_ranks(body)
+    return body
 
 
 def _child(name):
-    """the two rank threads live in a child process: each rank's stream needs a hardware queue of its own
-    (GPU_MAX_HW_QUEUES, read when the runtime starts) -- a rank's stream-side wait must not sit in front of
-    the other rank's copies"""
+    """the two ranks are two child processes: each has hardware queues of its own, so a rank's stream-side wait
+    never sits in front of the other rank's copies (ranks that are threads of one process can share a queue)"""
     from test_gpu_multirank import _fake_rccl
-    env = dict(os.environ, LBFGSB_FAKE_RCCL_SO=_fake_rccl(), GPU_MAX_HW_QUEUES="8")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name], env=env, capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads(r.stdout.strip().splitlines()[-1]), r.stderr
+    so = _fake_rccl()
+    uid = UniqueId()
+    assert _lib_at(so).ncclGetUniqueId(C.byref(uid)) == 0
+    env = dict(os.environ, LBFGSB_FAKE_RCCL_SO=so)
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), name, str(rank), bytes(uid).hex()],
+                              env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+             for rank in range(2)]
+    outs = []
+    try:
+        for p in procs:
+            outs.append(p.communicate(timeout=300))
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+    err = "".join(e for _, e in outs)
+    assert [p.returncode for p in procs] == [0, 0], err[-3000:]
+    return [json.loads(o.strip().splitlines()[-1]) for o, _ in outs], err
 
 
 def test_all_gather_is_asynchronous_and_correct():
@@ -135,6 +134,5 @@ def test_unequal_counts_are_caught():
 
 
 if __name__ == "__main__":
-    sys.path.insert(0, HERE)
-    res = {"async": scenario_async, "mismatch": scenario_mismatch}[sys.argv[1]]()
-    print(json.dumps(res))
+    body = {"async": scenario_async, "mismatch": scenario_mismatch}[sys.argv[1]]()
+    print(json.dumps(_one_rank(body, int(sys.argv[2]), sys.argv[3])))

@@ -14,10 +14,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(os.path.dirname(HERE), "lbfgsb_amd", "fortran", "build")
+# the reference's drivers are built from its sources (oracle/Makefile, target fortran_drivers) under oracle/_ref/;
+# examples/driver_dev.f90 is the library's own (lbfgsb_amd/fortran/build)
+DRIVERS = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "fortran")
+BUILD = os.path.join(DRIVERS, "build")
 # the same module and drivers compiled with -fdefault-integer-8 (8-byte INTEGER and LOGICAL: n, m, nbd,
 # iwa, isave, lsave, iprint), the build BASELINE.md section 3 calls mandatory for n = 1e8
-BUILD_I8 = os.path.join(os.path.dirname(HERE), "lbfgsb_amd", "fortran", "build_i8")
+BUILD_I8 = os.path.join(DRIVERS, "build_i8")
 BUILDS = [pytest.param(BUILD, id="int32"), pytest.param(BUILD_I8, id="int64")]
 GOLD = os.path.join(HERE, "golden", "ref_outputs")
 
@@ -151,32 +154,37 @@ def test_driver1_as_a_plain_c_program(tmp_path):
     assert abs(float(mm.group(3)) - 1.0834900834300614e-09) <= 1e-6 * 1.0834900834300614e-09, out
 
 
-@pytest.mark.parametrize("spec,iprint", [
+# random problems of tests/test_gpu_fuzz.py at one iprint each; what the real reference printed for them is on file
+# (tests/golden/ref_outputs/live_*, recorded from oracle/_ref by tests/golden/make_golden.py)
+LIVE_CASES = [
     ("fuzz:90001:400:1:13", 1), ("fuzz:90003:60:1:13", 99), ("fuzz:90004:40:1:13", 100), ("fuzz:90005:16:1:13", 101),
     ("fam:linear:91003", 1), ("fam:linear:91002", 99), ("fam:rosenchain:91003", 100), ("fam:scaled:91000", 0),
-])
+]
+
+
+def live_case_name(spec, iprint):
+    """file name stem of a LIVE_CASES transcript: <stem>.txt (stdout), <stem>_iterate.txt (the iteration file)"""
+    return "live_%s_iprint%d" % (spec.replace(":", "_"), iprint)
+
+
+@pytest.mark.parametrize("spec,iprint", LIVE_CASES)
 def test_transcripts_against_the_live_reference(tmp_path, spec, iprint):
-    """Printed output on problems no golden file covers: the real reference (oracle/_ref, a built library that
-    travels to the GPU box) and the library through the reference-shaped host entry run the same random problem
-    at the same iprint; stdout and the iteration file are compared word for word, numbers to print precision
+    """Printed output on problems the driver transcripts do not cover: the library through the reference-shaped
+    host entry runs a random problem at a given iprint, and its stdout and iteration file are compared word for
+    word, numbers to print precision, with what the real reference (oracle/_ref) printed for the same run
     (profiles/scripts/transcript_sweep.py runs hundreds of these; the problems here are ones whose trajectory
     does not leave the reference's by rounding drift)."""
-    from oracle import pyoracle as po
-    if not po.Engine.available("ref"):
-        pytest.skip("oracle/_ref not built")
     worker = os.path.join(HERE, "_iprint_worker.py")
-    outs = {}
-    for eng in ("ref", "gpu"):
-        cwd = tmp_path / eng
-        cwd.mkdir()
-        r = subprocess.run([os.sys.executable, worker, eng, spec, "0", "0", str(iprint), "25"], cwd=str(cwd),
-                           capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, (eng, r.stderr[-1500:])
-        itf = cwd / "iterate.dat"
-        outs[eng] = (r.stdout.splitlines(), itf.read_text().splitlines() if itf.exists() else [])
-    assert len(outs["ref"][0]) > 3
-    compare(outs["gpu"][0], outs["ref"][0])
-    compare(outs["gpu"][1], outs["ref"][1])
+    r = subprocess.run([os.sys.executable, worker, "gpu", spec, "0", "0", str(iprint), "25"], cwd=str(tmp_path),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-1500:]
+    itf = tmp_path / "iterate.dat"
+    got = (r.stdout.splitlines(), itf.read_text().splitlines() if itf.exists() else [])
+    stem = os.path.join(GOLD, live_case_name(spec, iprint))
+    want = (open(stem + ".txt").read().splitlines(), open(stem + "_iterate.txt").read().splitlines())
+    assert len(want[0]) > 3
+    compare(got[0], want[0])
+    compare(got[1], want[1])
 
 
 def test_device_pointer_example_with_the_callers_own_kernel(tmp_path):
@@ -219,8 +227,8 @@ def test_device_pointer_example_with_the_callers_own_kernel(tmp_path):
 # driver1 stops after ONE iteration (factr * epsmch = 1.19 > any relative reduction), driver2 / driver3
 # run into fp32's floor near f ~ 1e-12 instead of reaching their |proj g| < 1e-10 stop.
 # ---------------------------------------------------------------------------------------------
-BUILD_R32 = os.path.join(os.path.dirname(HERE), "lbfgsb_amd", "fortran", "build_r32")
-BUILD_R32_I8 = os.path.join(os.path.dirname(HERE), "lbfgsb_amd", "fortran", "build_r32_i8")
+BUILD_R32 = os.path.join(DRIVERS, "build_r32")
+BUILD_R32_I8 = os.path.join(DRIVERS, "build_r32_i8")
 BUILDS_R32 = [pytest.param(BUILD_R32, id="real32-int32"), pytest.param(BUILD_R32_I8, id="real32-int64")]
 
 
@@ -282,7 +290,7 @@ ROW = re.compile(r"^\s*Iterate\s+(\d+)\s+nfg =\s*(\d+)\s+f =\s*(\S+)\s+\|proj g\
 
 
 def run_driver_dev(n, m, iters, warm, mode="pp", compact=False):
-    exe = os.path.join(BUILD, "driver_dev")
+    exe = os.path.join(os.path.dirname(HERE), "lbfgsb_amd", "fortran", "build", "driver_dev")
     if not os.path.exists(exe):
         pytest.skip("%s not built (needs amdflang at build time)" % exe)
     r = subprocess.run([exe, str(n), str(m), str(iters), str(warm), mode] + (["compact"] if compact else []),

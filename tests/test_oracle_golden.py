@@ -1,6 +1,7 @@
 """Pin the CPU oracle (oracle/lbfgsb_oracle.c) against golden vectors that the
-REAL reference produced (tests/golden/make_golden.py), and, when it is built,
-against the reference itself (oracle/_ref).  CPU only."""
+REAL reference produced (tests/golden/make_golden.py).  CPU only."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -143,17 +144,30 @@ def test_oracle_matches_reference_transcript_numbers(oracle_built):
         assert a[6] == pytest.approx(b[6], rel=2e-3)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref",
-                                                    "liblbfgsb_ref.so")),
-                    reason="oracle/_ref not built (no reference sources here)")
+# a size and (n, m) that are NOT in the fixtures: every state array after every setulb return, by digest
+LIVE_PROBLEMS = {"quad3000_m7_mixed": lambda po: po.problem_quadratic(3000, 7, mixed_nbd=True),
+                 "rosen501_m4": lambda po: po.problem_rosenbrock(501, 4, 0.0, 0.0)}
+LIVE_FIELDS = ("x", "g", "f", "wa", "iwa", "task", "csave", "lsave", "isave", "dsave")
+LIVE_DIGESTS = os.path.join(GOLD, "live_ref_state_digests.json")
+
+
+def state_digests(po, engine, p):
+    """per setulb return (at most 120): {field: sha256 of its bytes, wall-clock slots masked}"""
+    out = []
+    po.run(po.Engine(engine), p, max_calls=120, snapshot=lambda k, s: out.append(
+        {nm: hashlib.sha256(_mask(nm, getattr(s, nm)).tobytes()).hexdigest() for nm in LIVE_FIELDS}))
+    return out
+
+
 def test_oracle_bit_identical_to_live_reference(oracle_built):
-    """A size and (n, m) that are NOT in the fixtures, against the live reference."""
+    """A size and (n, m) that are NOT in the fixtures, bit for bit against what the reference (oracle/_ref) left in
+    every state array after every return (tests/golden/live_ref_state_digests.json, make_golden.py)."""
     po = oracle_built
-    for p in (po.problem_quadratic(3000, 7, mixed_nbd=True), po.problem_rosenbrock(501, 4, 0.0, 0.0)):
-        a, b = [], []
-        po.run(po.Engine("oracle"), p, max_calls=120, snapshot=lambda k, s: a.append(s.copy()))
-        po.run(po.Engine("ref"), p, max_calls=120, snapshot=lambda k, s: b.append(s.copy()))
-        assert len(a) == len(b)
-        for sa, sb in zip(a, b):
-            for nm in ("x", "g", "f", "wa", "iwa", "task", "csave", "lsave", "isave", "dsave"):
-                assert _mask(nm, getattr(sa, nm)).tobytes() == _mask(nm, getattr(sb, nm)).tobytes(), nm
+    want = json.load(open(LIVE_DIGESTS))
+    assert sorted(want) == sorted(LIVE_PROBLEMS)
+    for name, mk in LIVE_PROBLEMS.items():
+        a, b = state_digests(po, "oracle", mk(po)), want[name]
+        assert len(a) == len(b) > 0, name
+        for k, (sa, sb) in enumerate(zip(a, b)):
+            for nm in LIVE_FIELDS:
+                assert sa[nm] == sb[nm], (name, k, nm)
