@@ -332,6 +332,41 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
                             const int32_t *isave);
 
 /* -------------------------------------------------------------------------
+ * The curvature model as a device operator.
+ * At a setulb return the context holds what the reference's wa holds there: col stored pairs (s_j, y_j) -- the
+ * columns of Ws / Wy in ring order from head --, theta (dsave(1)), Sy (L + D of S'Y), Ss (upper triangle of S'S)
+ * and Wt (formt's Cholesky factor).  From them, with W = [Y, theta S] and M the 2col x 2col middle matrix of bmv:
+ *   LBFGSB_QN_B:  B = theta I - W M W'  -- the matrix whose products bmv forms (src/lbfgsb.f90:1057-1123), that is
+ *                 theta I updated by the col BFGS updates in ring order (col = 0: B = theta I);
+ *   LBFGSB_QN_H:  H = B^-1, in the compact form of Byrd, Nocedal and Schnabel:
+ *                 H = theta^-1 I + [S, theta^-1 Y] [[R^-T (D + theta^-1 Y'Y) R^-1, -R^-T], [-R^-1, 0]] [S'; theta^-1 Y']
+ *                 with R the upper triangle of S'Y (diagonal included).  R's strict upper part and Y'Y are not state
+ *                 the iteration keeps: one Gram pass over all rows computes them, once per set of pairs.
+ * H starts from the solver's own theta (scipy's LbfgsInvHessProduct starts from H0 = I): it is exactly the inverse
+ * of the matrix the solver uses.
+ *
+ * qn_apply: out_j = A v_j for k vectors (A = B or H), vector j at v + j*ldv, result j at out + j*ldo (ldv, ldo >=
+ *   n_local; device memory of the context's real kind; out may not overlap v).  qn_diag: out = diag(A) (n_local
+ *   reals), at most 32 stored pairs (a per-row quadratic form of width 2col: LBFGSB_E_ARG beyond).
+ * The entries read the pairs of the context's last return, or of the last import_state (theta then y'y / s'y of the
+ * newest pair, as matupd computes it).  They are valid at every return at which lbfgsb_hip_export_state is
+ * (FG_START, NEW_X, FG_LNSRCH unless its set-up is deferred, CONVERGENCE / ABNORMAL / STOP) and after
+ * lbfgsb_hip_minimize.  LBFGSB_E_STATE, changing nothing: a deferred line-search set-up is live, a built-in
+ * objective's value is still on the device, or the context has no run.  LBFGSB_E_ARG: NULL, k < 1, ld < n_local.
+ * Calling them changes nothing the run computes: every later return is bit-identical with or without the calls.
+ * Streams: as lbfgsb_hip_setulb_dev -- v is read on the context's stream; out is complete when the call returns,
+ * or, with LBFGSB_F_NO_RETURN_SYNC, ordered on that stream (lbfgsb_hip_return_event).  qn_apply waits for its
+ * sums on the host once per 4 vectors.  Several ranks: every rank calls collectively with its own rows; the sums
+ * are reduced as the iteration's (rank order / the host reducer), so every rank uses the same coefficients.
+ * REAL32 contexts: v and out are fp32, every sum fp64.
+ * ------------------------------------------------------------------------- */
+#define LBFGSB_QN_B 0
+#define LBFGSB_QN_H 1
+int lbfgsb_hip_qn_apply(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, void *out,
+                        int64_t ldo);
+int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out);
+
+/* -------------------------------------------------------------------------
  * Per-kernel entry points (one per row of SURVEY.md 8a), for parity tests
  * and profiling.  All pointers are DEVICE pointers unless named h_*.
  * Reduction results come back in host doubles, already complete across

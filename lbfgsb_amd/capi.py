@@ -50,6 +50,8 @@ PROTOTYPES = {
     "lbfgsb_hip_minimize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int,
                                       C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "lbfgsb_hip_export_state": (C.c_int, [_vp, _vp, _vp]),
+    "lbfgsb_hip_qn_apply": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
+    "lbfgsb_hip_qn_diag": (C.c_int, [_vp, C.c_int, _vp]),
     "lbfgsb_hip_import_state": (C.c_int, [_vp, _vp, _vp, _vp]),
     "lbfgsb_hip_projgr": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lbfgsb_hip_wtv": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
@@ -86,6 +88,7 @@ PROTOTYPES = {
 }
 
 E_NOGPU, E_ARG, E_ALLOC, E_COMM, E_STATE = -100, -101, -102, -103, -104   # status codes of include/lbfgsb_hip.h
+QN_B, QN_H = 0, 1  # lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag: the model B, its inverse H = B^-1
 F_REAL32 = 1
 F_MIRROR_INDEX = 2
 F_NO_RETURN_SYNC = 4

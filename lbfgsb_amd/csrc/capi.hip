@@ -226,6 +226,19 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
   return ctx->import_state(wa, iwa, isave);
 }
 
+int lbfgsb_hip_qn_apply(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, void *out,
+                        int64_t ldo) {
+  if (!ctx || !v || !out) return fail(LBFGSB_E_ARG, "qn_apply: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_apply: mode");
+  if (k < 1 || ldv < ctx->n || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_apply: k < 1 or ld < n_local");
+  return ctx->qn_apply(mode, k, v, ldv, out, ldo);
+}
+int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out) {
+  if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_diag: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_diag: mode");
+  return ctx->qn_diag(mode, out);
+}
+
 int lbfgsb_hip_projgr(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u,
                       const int32_t *nbd, const void *g, double *h_sbgnrm) {
   if (!ctx || !x || !l || !u || !nbd || !g || !h_sbgnrm) return fail(LBFGSB_E_ARG, "projgr: NULL argument");

@@ -138,6 +138,90 @@ inline int formt(int m, double *wt_, const double *sy_, const double *ss_, int c
   return dpofa(wt, col) ? -3 : 0;
 }
 
+// ---- the curvature model as an operator (lbfgsb_hip_qn_apply / qn_diag, solver_qn.inl) ----
+// Both matrices are written over [S, Y] (logical column order, oldest pair first):
+//   B = theta I + S cs + Y cy,      (cs; cy) = N_B (S'v; Y'v)
+//   H = theta^-1 I + S cs + Y cy,   (cs; cy) = N_H (S'v; Y'v)
+// B is the matrix bmv's middle matrix defines: B = theta I - [Y, theta S] M [Y, theta S]'.  H = B^-1 in the
+// compact form of Byrd, Nocedal and Schnabel (1994, eq. 2.16 with gamma = 1 / theta):
+//   H = theta^-1 I + [S, theta^-1 Y] [[R^-T (D + theta^-1 Y'Y) R^-1, -R^-T], [-R^-1, 0]] [S'; theta^-1 Y']
+// with R the upper triangle of S'Y (diagonal included) and D its diagonal.
+
+// coefficients of B v: stv = S'v, ytv = Y'v (col each) -> cs, cy.  Returns bmv's info.
+inline int qn_coef_b(int m, const double *sy, const double *wt, int col, double theta, const double *stv,
+                     const double *ytv, double *cs, double *cy) {
+  if (col == 0) return 0;
+  double v[2 * 1024], p[2 * 1024];
+  for (int i = 0; i < col; ++i) v[i] = ytv[i], v[col + i] = theta * stv[i];
+  const int info = bmv(m, sy, wt, col, v, p);
+  if (info) return info;
+  for (int i = 0; i < col; ++i) cy[i] = -p[i], cs[i] = -(theta * p[col + i]);
+  return 0;
+}
+
+// coefficients of H v.  sty: S'Y (col x col, leading dimension ldg: sty[i + k ldg] = s_i'y_k), yty: Y'Y (same
+// layout), dg: the diagonal s_i'y_i the iteration keeps (sy), which is also R's.  Returns 0, or i + 1 when
+// R(i, i) <= 0 (no pair is stored without s'y > 0: reference src/lbfgsb.f90:820-826).
+inline int qn_coef_h(int col, double theta, const double *sty, const double *yty, int ldg, const double *dg,
+                     const double *stv, const double *ytv, double *cs, double *cy) {
+  if (col == 0) return 0;
+  for (int i = 0; i < col; ++i)
+    if (!(dg[i] > 0.0)) return i + 1;
+  const double ti = 1.0 / theta;
+  double u[1024], w[1024];
+  for (int i = col - 1; i >= 0; --i) {  // u = R^-1 S'v
+    double s = stv[i];
+    for (int k = i + 1; k < col; ++k) s = s - sty[i + (size_t)k * ldg] * u[k];
+    u[i] = s / dg[i];
+  }
+  for (int i = 0; i < col; ++i) {  // w = (D + theta^-1 Y'Y) u - theta^-1 Y'v
+    double s = 0.0;
+    for (int k = 0; k < col; ++k) s = s + yty[i + (size_t)k * ldg] * u[k];
+    w[i] = dg[i] * u[i] + ti * s - ti * ytv[i];
+  }
+  for (int i = 0; i < col; ++i) {  // cs = R^-T w
+    double s = w[i];
+    for (int k = 0; k < i; ++k) s = s - sty[k + (size_t)i * ldg] * cs[k];
+    cs[i] = s / dg[i];
+  }
+  for (int i = 0; i < col; ++i) cy[i] = -(ti * u[i]);
+  return 0;
+}
+
+// N (2col x 2col, column-major, leading dimension 2col) of a coefficient map coef(stv, ytv, cs, cy): column k is
+// the map of the k-th unit vector; then symmetrised, (N + N') / 2 (the exact matrix is symmetric).
+template <typename F>
+inline int qn_nmat(int col, F &&coef, double *nm) {
+  const int d = 2 * col;
+  double e[2 * 1024], c[2 * 1024];
+  for (int k = 0; k < d; ++k) {
+    for (int i = 0; i < d; ++i) e[i] = i == k ? 1.0 : 0.0;
+    const int info = coef(e, e + col, c, c + col);
+    if (info) return info;
+    for (int i = 0; i < d; ++i) nm[i + (size_t)k * d] = c[i];
+  }
+  for (int k = 0; k < d; ++k)
+    for (int i = k + 1; i < d; ++i) {
+      const double s = 0.5 * (nm[i + (size_t)k * d] + nm[k + (size_t)i * d]);
+      nm[i + (size_t)k * d] = nm[k + (size_t)i * d] = s;
+    }
+  return 0;
+}
+
+// N as the diagonal kernel reads it: rows / columns padded to mc pairs (S block 0..mc, Y block mc..2mc), the upper
+// triangle row by row, off-diagonal entries doubled (r'Nr = sum_a r_a (N_aa r_a + sum_{b > a} 2 N_ab r_b)).
+inline void qn_pack_n(int col, int mc, const double *nm, double *np) {
+  const int d = 2 * col, dp = 2 * mc;
+  auto at = [&](int a) { return a < mc ? (a < col ? a : -1) : (a - mc < col ? col + a - mc : -1); };
+  int e = 0;
+  for (int a = 0; a < dp; ++a)
+    for (int b = a; b < dp; ++b) {
+      const int ia = at(a), ib = at(b);
+      const double v = ia < 0 || ib < 0 ? 0.0 : nm[ia + (size_t)ib * d];
+      np[e++] = a == b ? v : 2.0 * v;
+    }
+}
+
 // ---- 60-byte blank padded strings (Fortran character(len=60)) ----
 inline void str60_set(char *t, const char *s) {
   size_t k = std::strlen(s);

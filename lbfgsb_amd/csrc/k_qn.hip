@@ -1,0 +1,294 @@
+// k_qn.hip -- the limited-memory curvature model as a device operator (lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag,
+// solver_qn.inl).  (part of the gfx950 kernel set; kernels_common.hpp has the overview)
+//
+// B = theta I + [S, Y] N_B [S, Y]'   and   H = B^-1 = theta^-1 I + [S, Y] N_H [S, Y]'
+// with the 2col x 2col matrices N formed on the host (host_dense.hpp, qn_coef_b / qn_coef_h).  Three passes:
+//   qn_wtv     [S'v; Y'v] for K vectors at once (every W entry read once per block of K vectors);
+//   qn_expand  out_j = alpha src_j + S cs_j + Y cy_j (coefficients as kernel arguments);
+//   qn_diag    out_i = alpha + r_i' N r_i,  r_i = row i of [S, Y], N in LDS (upper triangle, off-diagonal doubled).
+// None of them writes W: they read it in the layout it is in (natural order, or the tile-local layout of k_layout.hip
+// through the lmask bits), and v / out are always in natural row order.  Columns are processed in tiles of at most
+// 16 (qn_wtv, qn_expand: any number of pairs) or all at once up to 32 (qn_diag).  Reductions: per-lane fp64
+// accumulators -> block_reduce_store -> one partial per workgroup -> qn_finalize in a fixed order, into buffers of
+// the operator's own (never the iteration's q.d_part / q.d_res).  Nothing here touches the Queue's counters.
+#include "kernels_common.hpp"
+
+namespace lbk {
+
+template <bool CW>
+__device__ __forceinline__ int64_t qn_slot(const uint64_t *__restrict__ lmask, int64_t i) {
+  if constexpr (CW) return wrow(lmask, i);
+  else return i;
+}
+
+// sums: slot kk * 2MC + j = S(:, c0 + j)' v_kk, slot kk * 2MC + MC + j = Y(:, c0 + j)' v_kk (j >= col - c0: zero).
+// VSLOT: vector row i is read at the SLOT of row i (the vectors are columns of W themselves: the Gram).
+template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_wtv_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                       int col, int c0, const uint64_t *__restrict__ lmask,
+                                                       QnVecs<T> v, double *part) {
+  static_assert(!CW || V == 1, "the layout is read one row per lane");
+  double acc[2 * MC * K];
+#pragma unroll
+  for (int k = 0; k < 2 * MC * K; ++k) acc[k] = 0.0;
+  for_rows<T, V>(n, [&](int64_t i, auto wt) {
+    constexpr int W = decltype(wt)::value;
+    const int64_t s = qn_slot<CW>(lmask, i);
+    double vv[K][W], a[MC][W], b[MC][W];
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) ldx<W, NT>(v.p[kk] + (VSLOT ? s : i), vv[kk]);
+#pragma unroll
+    for (int j = 0; j < MC; ++j) {
+      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
+      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
+      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
+    }
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk)
+#pragma unroll
+      for (int j = 0; j < MC; ++j)
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+          acc[kk * 2 * MC + j] += a[j][w] * vv[kk][w];
+          acc[kk * 2 * MC + MC + j] += b[j][w] * vv[kk][w];
+        }
+  });
+  block_reduce_store<2 * MC * K>(acc, 2 * MC * K, 0, 0, part, MAX_BLOCKS);
+}
+
+// res[k] = sum over the workgroups' partials of slot k, in a fixed order (one workgroup per slot)
+__global__ __launch_bounds__(BLOCK) void qn_finalize_kernel(const double *__restrict__ part, int nblocks,
+                                                            double *__restrict__ res) {
+  __shared__ double sm[BLOCK];
+  const int k = blockIdx.x;
+  double v = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += BLOCK) v += part[(size_t)k * MAX_BLOCKS + b];
+  sm[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = BLOCK / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) res[k] = sm[0];
+}
+
+// out_kk[i] = alpha src_kk[i] + sum_j cf.c[kk][j] S(i, c0 + j) + cf.c[kk][MC + j] Y(i, c0 + j)
+template <typename T, int MC, int K, int V, bool CW, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_expand_kernel(int64_t n, const T *__restrict__ ws,
+                                                          const T *__restrict__ wy, const T *__restrict__ zero,
+                                                          int64_t ldw, int m, int head, int col, int c0,
+                                                          const uint64_t *__restrict__ lmask, QnCoef<MC, K> cf,
+                                                          QnVecs<T> src, QnOuts<T> out) {
+  static_assert(!CW || V == 1, "the layout is read one row per lane");
+  for_rows<T, V>(n, [&](int64_t i, auto wt) {
+    constexpr int W = decltype(wt)::value;
+    const int64_t s = qn_slot<CW>(lmask, i);
+    double x[K][W], a[MC][W], b[MC][W];
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) ldx<W, false>(src.p[kk] + i, x[kk]);
+#pragma unroll
+    for (int j = 0; j < MC; ++j) {
+      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
+      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
+      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
+    }
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) {
+      double o[W];
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        double e = cf.alpha * x[kk][w];
+#pragma unroll
+        for (int j = 0; j < MC; ++j) {
+          e += cf.c[kk][j] * a[j][w];
+          e += cf.c[kk][MC + j] * b[j][w];
+        }
+        o[w] = e;
+      }
+      stnt<W>(out.p[kk] + i, o);
+    }
+  });
+}
+
+// out[i] = alpha + r' N r, r = (S(i, 0..MC), Y(i, 0..MC)); np = the packed upper triangle of N (row-major over
+// a <= b, off-diagonal entries doubled), (2MC)(2MC + 1)/2 doubles, staged in LDS once per workgroup
+template <typename T, int MC, bool CW, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_diag_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                        const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                        int col, const uint64_t *__restrict__ lmask,
+                                                        const double *__restrict__ np, double alpha,
+                                                        T *__restrict__ out) {
+  constexpr int D = 2 * MC, NP = D * (D + 1) / 2;
+  __shared__ double sn[NP];
+  for (int e = threadIdx.x; e < NP; e += BLOCK) sn[e] = np[e];
+  __syncthreads();
+  for_rows<T, 1>(n, [&](int64_t i, auto) {
+    // (N is re-read from LDS for every row: hoisted out of the row loop, its 2080 entries at 32 pairs would live
+    //  in registers and spill to scratch -- the memory clobber keeps the reads here)
+    asm volatile("" ::: "memory");
+    const int64_t s = qn_slot<CW>(lmask, i);
+    double r[D][1];
+#pragma unroll
+    for (int j = 0; j < MC; ++j) {
+      const int64_t off = col_off(j, col, head, m, ldw) + s;
+      ld_col<T, 1, NT>(j < col, ws + off, zero, r[j]);
+      ld_col<T, 1, NT>(j < col, wy + off, zero, r[MC + j]);
+    }
+    double acc = 0.0;
+    int e = 0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      double t = 0.0;
+#pragma unroll
+      for (int b = a; b < D; ++b) t += sn[e++] * r[b][0];
+      acc += r[a][0] * t;
+    }
+    const double o[1] = {alpha + acc};
+    stnt<1>(out + i, o);
+  });
+}
+
+// ---------------------------------------------------------------- launches
+namespace {
+template <typename T>
+bool aligned_for(const T *p, int v) {
+  return ((uintptr_t)p % ((uintptr_t)v * sizeof(T))) == 0;
+}
+}  // namespace
+
+int qn_mc(int ncols) { return ncols <= 5 ? 5 : (ncols <= 10 ? 10 : QN_TILE); }
+int qn_kmax(int mc) { return mc <= 10 ? 4 : 2; }
+
+#define QN_DISPATCH_MC(mc, ...)   \
+  do {                            \
+    if ((mc) == 5) {              \
+      constexpr int MC = 5;       \
+      __VA_ARGS__;                \
+    } else if ((mc) == 10) {      \
+      constexpr int MC = 10;      \
+      __VA_ARGS__;                \
+    } else {                      \
+      constexpr int MC = QN_TILE; \
+      __VA_ARGS__;                \
+    }                             \
+  } while (0)
+#define QN_DISPATCH_K(k, ...)                 \
+  do {                                        \
+    if ((k) == 1) {                           \
+      constexpr int K = 1;                    \
+      __VA_ARGS__;                            \
+    } else if ((k) == 2) {                    \
+      constexpr int K = 2;                    \
+      __VA_ARGS__;                            \
+    } else if constexpr (MC <= 10) {          \
+      constexpr int K = 4;                    \
+      __VA_ARGS__;                            \
+    }                                         \
+  } while (0)
+#define QN_DISPATCH_BOOL(c, NAME, ...) \
+  do {                                 \
+    if (c) {                           \
+      constexpr bool NAME = true;      \
+      __VA_ARGS__;                     \
+    } else {                           \
+      constexpr bool NAME = false;     \
+      __VA_ARGS__;                     \
+    }                                  \
+  } while (0)
+// the tile-local layout exists for fp64 and m <= 10 only (Solver::cw_eligible): no other CW instantiation.  A layout
+// handed to any other combination launches nothing (the caller reports hipErrorInvalidValue): never natural-order
+// reads of a permuted W
+#define QN_DISPATCH_CW(lm, ...)                                 \
+  do {                                                          \
+    if constexpr (sizeof(T) == 8 && MC <= 10) {                 \
+      if (lm) {                                                 \
+        constexpr bool CW = true;                               \
+        constexpr int V = 1;                                    \
+        __VA_ARGS__;                                            \
+        break;                                                  \
+      }                                                         \
+    }                                                           \
+    if (lm) break;                                              \
+    constexpr bool CW = false;                                  \
+    if (vec2) {                                                 \
+      constexpr int V = 2;                                      \
+      __VA_ARGS__;                                              \
+    } else {                                                    \
+      constexpr int V = 1;                                      \
+      __VA_ARGS__;                                              \
+    }                                                           \
+  } while (0)
+
+template <typename T>
+hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                         QnVecs<T> v, bool vslot, double *part, double *res) {
+  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
+  // (two rows per lane only where operands + accumulators leave room for them: 2 mc k <= 20 sums)
+  bool vec2 = !vslot && 2 * mc * k <= 20;
+  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
+  int g = 0;
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(vslot, VS, QN_DISPATCH_BOOL(q.nt, NT, {
+    auto kern = qn_wtv_kernel<T, MC, K, V, CW, VS, NT>;
+    g = grid_for_w(q, n, V, (const void *)kern);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
+                       w.lmask, v, part);
+  })))));
+  if (g == 0) return hipErrorInvalidValue;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(qn_finalize_kernel, dim3(2 * mc * k), dim3(BLOCK), 0, q.stream, (const double *)part, g, res);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_qn_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                            const double *coef, double alpha, QnVecs<T> src, QnOuts<T> out) {
+  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
+  bool vec2 = 2 * mc * k <= 20;
+  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(src.p[kk], 2) && aligned_for((const T *)out.p[kk], 2);
+  bool done = false;
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
+    QnCoef<MC, K> cf{};
+    cf.alpha = alpha;
+    for (int kk = 0; kk < K; ++kk)
+      for (int j = 0; j < 2 * MC; ++j) cf.c[kk][j] = coef[(size_t)kk * 2 * MC + j];
+    auto kern = qn_expand_kernel<T, MC, K, V, CW, NT>;
+    const int g = grid_for_w(q, n, V, (const void *)kern);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
+                       w.lmask, cf, src, out);
+    done = true;
+  }))));
+  if (!done) return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int col, const double *np, double alpha,
+                          T *out) {
+  const bool vec2 = false;
+  bool done = false;
+  DISPATCH_MAXC(col, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
+    if constexpr (V == 1) {
+      auto kern = qn_diag_kernel<T, MC, CW, NT>;
+      const int g = grid_for_w(q, n, 1, (const void *)kern);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col,
+                         w.lmask, np, alpha, out);
+      done = true;
+    }
+  })));
+  if (!done) return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+#define QN_INST(T)                                                                                                  \
+  template hipError_t launch_qn_wtv<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
+                                       bool, double *, double *);                                                 \
+  template hipError_t launch_qn_expand<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,          \
+                                          const double *, double, QnVecs<T>, QnOuts<T>);                         \
+  template hipError_t launch_qn_diag<T>(const Queue &, int64_t, WStore<T>, int, int, const double *, double, T *);
+QN_INST(double)
+QN_INST(float)
+#undef QN_INST
+
+}  // namespace lbk

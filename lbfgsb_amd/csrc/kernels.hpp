@@ -532,4 +532,39 @@ void finalize_flush(Queue &q);  // launch the parked jobs alone (a fetch that no
 void launch_publish(Queue &q, const double *src, double *dst_host, int count, unsigned long long seq,
                     unsigned long long *flag_host);
 
+// ---- the curvature model as a device operator (k_qn.hip, solver_qn.inl) ----
+// Column tiles of at most QN_TILE pairs per launch of the W'V and expand passes (any number of pairs: one launch per
+// tile); blocks of K = 1, 2 or 4 vectors per launch (qn_kmax: K <= 4 up to 10 columns per tile, K <= 2 beyond).
+constexpr int QN_TILE = 16;
+constexpr int QN_KMAX = 4;
+int qn_mc(int ncols);  // column capacity (5, 10, QN_TILE) of a tile of ncols <= QN_TILE pairs
+int qn_kmax(int mc);
+template <typename T>
+struct QnVecs {  // the vectors of a block, each of n rows in natural order
+  const T *p[QN_KMAX];
+};
+template <typename T>
+struct QnOuts {
+  T *p[QN_KMAX];
+};
+template <int MC, int K>
+struct QnCoef {  // out_k = alpha src_k + S c[k][0..MC) + Y c[k][MC..2MC): <= 4 x 2 x 10 doubles of kernel arguments
+  double c[K][2 * MC];
+  double alpha;
+};
+// [S'v_k; Y'v_k] of the columns c0 .. c0 + mc - 1 (those >= col give zeros): partials into part ([slot][MAX_BLOCKS]),
+// then a fixed-order finalize into res[k * 2 mc + j] (j < mc: S, j >= mc: Y).  vslot: the vectors are columns of W
+// (row i read at its slot in the layout).  w.lmask may be set: the layout is read as it is.
+template <typename T>
+hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                         QnVecs<T> v, bool vslot, double *part, double *res);
+// out_k = alpha src_k + [S, Y](:, tile) coef[k * 2 mc ...] (src_k may be out_k: the second and later tiles)
+template <typename T>
+hipError_t launch_qn_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                            const double *coef, double alpha, QnVecs<T> src, QnOuts<T> out);
+// out_i = alpha + r_i' N r_i (col <= 32; np: packed upper triangle of the maxc_for(col)-padded N, off-diagonal doubled)
+template <typename T>
+hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int col, const double *np, double alpha,
+                          T *out);
+
 }  // namespace lbk

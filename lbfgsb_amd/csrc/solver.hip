@@ -142,6 +142,7 @@ class Solver final : public lbfgsb_hip_ctx {
   ~Solver() override { release(); }
 
   void release() {
+    qn_release();
     if (debug_walk && n_mid > 0)
       std::fprintf(stderr, "[host] %lld stretches, us each: linesearch+return %.1f | caller %.1f | update %.1f | "
                            "cauchy+freev %.1f | formk+subsm algebra %.1f | all %.1f\n",
@@ -628,6 +629,7 @@ class Solver final : public lbfgsb_hip_ctx {
     dsave[5] = cpu1, dsave[6] = cachyt, dsave[7] = sbtime, dsave[8] = lnscht, dsave[9] = time1;
     dsave[10] = gd, dsave[11] = stpmx, dsave[12] = sbgnrm, dsave[13] = stp, dsave[14] = gdold;
     dsave[15] = dtd;
+    qn_record(col, head, theta, iupdat);
   }
   void finish(Mainlb &L) {  // :892-902
     MAINLB_VIEW(L);
@@ -669,6 +671,7 @@ class Solver final : public lbfgsb_hip_ctx {
     spec.valid = false, pend.on = 0, pend.impl = 0, d_impl = z_in_x = false, scan.ready = false;
     ls.deferred = false, defer_live = false, wl.pending = false;
     nrefresh = 0;
+    qn.gen++;  // (a new run: whatever pairs the last one left are gone)
     live_head = 1, live_col = 0, cw_stale = 0, cw_hold = 0, cw_settled = 0;  // (no pair is stored: any layout bits may stay)
     sfv.valid = false, sfv_hot = false, eager.valid = false, spec_live_len = 0;
     spcand.valid = false, last_tsum = 0.0, last_dtm0 = 0.0, iter_seen = 0, spec_factor = 2.0, last_walk_nseg = 0;
@@ -1832,6 +1835,7 @@ class Solver final : public lbfgsb_hip_ctx {
 
 #include "solver_state.inl"     // state exchange, per-kernel doors, communicators
 #include "solver_doors.inl"     // routine doors (active, errclb, cauchy, freev, formk, cmprlb, subsm, lnsrlb, matupd)
+#include "solver_qn.inl"        // the curvature model B, H = B^-1 as device operators (qn_apply, qn_diag)
 };
 
 }  // namespace

@@ -153,6 +153,9 @@ struct lbfgsb_hip_ctx {
                        double *sc, int32_t *ic, char *task, char *csave, int32_t *isave2, double *dsave13) = 0;
   virtual int r_matupd(const void *g, double stp, double dr, double dtd, int32_t *ip, double *theta_out) = 0;
   virtual int sync() = 0;
+  // the curvature model of the last return as a device operator (solver_qn.inl, lbfgsb_hip_qn_apply / qn_diag)
+  virtual int qn_apply(int mode, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) = 0;
+  virtual int qn_diag(int mode, void *out) = 0;
   // communicators (capi.hip): an initialised RCCL communicator / a host reducer for this context
   virtual int attach_rccl(ncclComm_t comm, int rank, int nranks) = 0;
   virtual ncclComm_t rccl_comm() const = 0;

@@ -240,6 +240,7 @@
     double rr = 0.0;
     std::vector<double> wsy, wss;
     CHK(wide_matupd((const T *)g, stp, head, col, wsy, wss, rr));
+    qn.gen++;
     matupd_small(col, iupdat, wsy.data(), wss.data(), stp == 1.0 ? dtd : stp * stp * dtd, dr);
     HIPCHK(hipStreamSynchronize(stream));
     ip[1] = col, ip[2] = head, ip[3] = itail;

@@ -136,6 +136,10 @@
     nfree_g = nfree_glob;
     nenter_g = isave_user[40];
     ileave_g = isave_user[39];
+    // the curvature model of the imported state: its pairs, theta from them (import_state has no dsave)
+    qn.gen++;
+    qn.have = true, qn.col = live_col, qn.head = live_head, qn.theta = 1.0, qn.theta_gram = true;
+    qn.iupdat = isave_user[30], qn.nref = nrefresh;
     return 0;
   }
 
@@ -209,6 +213,7 @@
     HIPCHK(hipSetDevice(device));
     lbk::launch_lmask_ones(q, n, lmask);  // (natural row order)
     cw_packed = false, cw_stale = 0, live_head = 1, live_col = m;
+    qn.gen++;
     HIPCHK(hipMemcpy2DAsync(ws, (size_t)ld * sizeof(T), hws, (size_t)n * sizeof(T),
                             (size_t)n * sizeof(T), m, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpy2DAsync(wy, (size_t)ld * sizeof(T), hwy, (size_t)n * sizeof(T),

@@ -42,6 +42,9 @@
       public :: lbfgsb_objective                       ! built-in device objectives (lbfgsb_hip_objective)
       public :: lbfgsb_set_option                      ! per-context switches (lbfgsb_hip_set_option): 'compact_w', ...
       public :: lbfgsb_error_message                   ! text of the last failure (lbfgsb_hip_last_error)
+      public :: lbfgsb_qn_apply, lbfgsb_qn_diag        ! the curvature model B, H = B^-1 of the last return on the
+                                                       ! device (lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag)
+      integer,parameter,public :: LBFGSB_QN_B = 0, LBFGSB_QN_H = 1
       ! flags of lbfgsb_create (include/lbfgsb_hip.h)
       integer,parameter,public :: LBFGSB_F_REAL32 = 1, LBFGSB_F_MIRROR_INDEX = 2, LBFGSB_F_NO_RETURN_SYNC = 4, &
                                   LBFGSB_F_PARALLEL_GCP = 8, LBFGSB_F_INDEX_TIES = 32, LBFGSB_F_DEFER_LNSRCH = 64
@@ -130,6 +133,19 @@
             real(c_double),value :: val
             integer(c_int) :: rc
          end function lbfgsb_hip_set_option
+         function lbfgsb_hip_qn_apply(ctx,mode,k,v,ldv,out,ldo) bind(C,name='lbfgsb_hip_qn_apply') result(rc)
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, v, out
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, ldv, ldo
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_apply
+         function lbfgsb_hip_qn_diag(ctx,mode,out) bind(C,name='lbfgsb_hip_qn_diag') result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr),value :: ctx, out
+            integer(c_int),value :: mode
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_diag
          function c_strlen(s) bind(C,name='strlen') result(k)
             import :: c_ptr, c_size_t
             type(c_ptr),value :: s
@@ -367,6 +383,25 @@
          rc = lbfgsb_hip_objective(ctx, int(kind, c_int), x, g, c_null_ptr)
       end if
       end subroutine lbfgsb_objective
+
+      ! The curvature model of the last return (include/lbfgsb_hip.h, "The curvature model as a device operator"):
+      ! mode LBFGSB_QN_B (B, bmv's matrix) or LBFGSB_QN_H (H = B^-1).  lbfgsb_qn_apply: out_j = A v_j for k vectors
+      ! of the context's real kind, vector j at v + j*ldv elements, result j at out + j*ldo (device buffers,
+      ! ldv, ldo >= n).  lbfgsb_qn_diag: out = diag(A), at most 32 stored pairs.  rc as the C entries return it.
+      subroutine lbfgsb_qn_apply(ctx, mode, k, v, ldv, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, v, out
+      integer,intent(in) :: mode, k, ldv, ldo
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_apply(ctx, int(mode, c_int), int(k, c_int64_t), v, int(ldv, c_int64_t), out, &
+                               int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_apply
+
+      subroutine lbfgsb_qn_diag(ctx, mode, out, rc)
+      type(c_ptr),intent(in) :: ctx, out
+      integer,intent(in) :: mode
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_diag(ctx, int(mode, c_int), out)
+      end subroutine lbfgsb_qn_diag
 
       function lbfgsb_error_message() result(msg)
       character(len=:),allocatable :: msg

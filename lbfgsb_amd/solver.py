@@ -80,6 +80,7 @@ class DeviceSolver:
         self.same_stream_objective = bool(same_stream_objective)
         self.stream_ordered = bool(stream_ordered) and not self.same_stream_objective
         self.n, self.m = int(n_local), int(m)
+        self.device = int(device)
         self.n_global = int(n_global if n_global is not None else n_local)
         self.row0 = int(row0)
         self.real = np.float32 if real32 else np.float64
@@ -327,6 +328,59 @@ class DeviceSolver:
         isave = np.ascontiguousarray(isave, np.int32)
         check(self.lib.lbfgsb_hip_import_state(self.h, _p(wa), _p(iwa), _p(isave)))
 
+    # ---- the curvature model as a device operator (include/lbfgsb_hip.h, lbfgsb_hip_qn_apply / qn_diag) ----
+    def _qn_vec(self, t, what):
+        import torch
+        want = torch.float32 if self.real == np.float32 else torch.float64
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == want):
+            raise TypeError("%s must be a CUDA tensor of dtype %s" % (what, want))
+        if t.dim() not in (1, 2) or t.shape[-1] != self.n or t.stride(-1) != 1:
+            raise ValueError("%s must have shape (n,) or (k, n) with n = %d rows per vector, contiguous per vector"
+                             % (what, self.n))
+        return t
+
+    def _qn_done(self):
+        if self.same_stream_objective or self.stream_ordered:
+            self.release_to_stream()  # (out is ordered on the solver's stream only: torch's stream waits for it)
+
+    def qn_apply(self, v, out=None, inverse: bool = False):
+        """out = B v (inverse=False) or H v = B^-1 v (inverse=True) for v of shape (n,) or (k, n): the limited-memory
+        model of the last return (or import_state), theta I updated by the stored pairs -- H is exactly the inverse
+        of the matrix the solver uses (scipy's hess_inv starts from H0 = I instead).  Returns out."""
+        v = self._qn_vec(v, "v")
+        if out is None:
+            import torch
+            out = torch.empty(v.shape, dtype=v.dtype, device=v.device)
+        out = self._qn_vec(out, "out")
+        if out.shape != v.shape:
+            raise ValueError("out must have the shape of v")
+        k = 1 if v.dim() == 1 else v.shape[0]
+        ldv = self.n if v.dim() == 1 else v.stride(0)
+        ldo = self.n if out.dim() == 1 else out.stride(0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_apply(self.h, capi.QN_H if inverse else capi.QN_B, k, v.data_ptr(), ldv,
+                                           out.data_ptr(), ldo))
+        self._qn_done()
+        return out
+
+    def qn_diag(self, out=None, inverse: bool = False):
+        """diag(B) or diag(H) as an (n,) tensor (at most 32 stored pairs).  Returns out."""
+        import torch
+        if out is None:
+            dt = torch.float32 if self.real == np.float32 else torch.float64
+            out = torch.empty(self.n, dtype=dt, device=torch.device("cuda", self.device))
+        out = self._qn_vec(out, "out")
+        if out.dim() != 1:
+            raise ValueError("out must have shape (n,)")
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_diag(self.h, capi.QN_H if inverse else capi.QN_B, out.data_ptr()))
+        self._qn_done()
+        return out
+
+    def qn_operator(self, inverse: bool = True) -> "QnOperator":
+        """H (default) or B as a small linear-operator object: hess_inv = sol.qn_operator() after minimize()."""
+        return QnOperator(self, inverse)
+
     def projgr(self, x, l, u, nbd, g) -> float:
         out = np.zeros(1)
         check(self.lib.lbfgsb_hip_projgr(self.h, _p(x), _p(l), _p(u), _p(nbd), _p(g), _p(out)))
@@ -542,3 +596,29 @@ class DeviceSolver:
         return dict(launches=a.value, syncs=b.value, cauchy_fullsorts=c.value, wait_seconds=w.value,
                     collectives=nc.value, collective_bytes=nb.value, freev_skipped=fs.value,
                     skip_scans_reused=sr.value, refreshes=rf.value)
+
+
+class QnOperator:
+    """The curvature model of a DeviceSolver's last return as a linear operator on this rank's rows: H = B^-1
+    (inverse=True, what scipy's L-BFGS-B returns as hess_inv, but starting from the solver's theta) or B.
+    op @ v and op.matvec(v) take an (n,) tensor, op.matmat(V) an (n, k) one (columns are vectors, as in scipy);
+    op.diagonal() is diag(A).  Every call reads the solver's state as it is at that moment."""
+
+    def __init__(self, solver: DeviceSolver, inverse: bool = True):
+        self.solver, self.inverse = solver, bool(inverse)
+        self.shape = (solver.n, solver.n)
+        self.dtype = np.dtype(solver.real)
+
+    def matvec(self, v):
+        return self.solver.qn_apply(v, inverse=self.inverse)
+
+    def matmat(self, vs):
+        if vs.dim() != 2 or vs.shape[0] != self.shape[1]:
+            raise ValueError("matmat takes an (n, k) tensor")
+        return self.solver.qn_apply(vs.t().contiguous(), inverse=self.inverse).t()
+
+    def diagonal(self):
+        return self.solver.qn_diag(inverse=self.inverse)
+
+    def __matmul__(self, v):
+        return self.matvec(v) if v.dim() == 1 else self.matmat(v)
