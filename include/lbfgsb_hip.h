@@ -93,7 +93,7 @@ enum {
                                 reference).  For callers who prefer the
                                 O(window) cost bound over the reference's tie order: the replay costs
                                 what the reference's own walk costs (heap pops over all breakpoints). */
-  LBFGSB_F_DEFER_LNSRCH = 64 /* for callers that evaluate f,g on the context's own stream and do nothing
+  LBFGSB_F_DEFER_LNSRCH = 64, /* for callers that evaluate f,g on the context's own stream and do nothing
                                 else with the context between an 'FG_LNSRCH' return and the re-entry with
                                 that evaluation (lbfgsb_hip_minimize with a built-in objective, bench.py).
                                 The pass that forms the subspace step also stores the first trial point
@@ -119,6 +119,28 @@ enum {
                                 Not with LBFGSB_F_MIRROR_INDEX, LBFGSB_F_PARALLEL_GCP or iprint >= 99: such
                                 contexts wait as before (m > LBFGSB_FUSED_M: deferred while col <= 96 and the
                                 options "wide_tail" / "wide_one" are on, the defaults). */
+  LBFGSB_F_FOLLOW_BOUNDS = 128 /* follow bounds that the caller edits during a run, as the reference does (it
+                                re-reads l, u, nbd on every call).  Every entry after 'START' compares the
+                                caller's l, u, nbd with the context's snapshot, bit for bit, before it
+                                launches anything that reads bounds: one pass over the three arrays (20 bytes
+                                per row in fp64 with uniform bounds, 37 with streamed ones) and one host sync.
+                                On a difference the snapshot is rebuilt and the call continues with the
+                                reference's semantics; products an earlier call computed ahead of time from the
+                                old bounds are dropped.  Other array pointers than in the last call count as
+                                a difference.  Such a context never returns 'ERROR: BOUNDS CHANGED DURING RUN'
+                                (option "bounds_check" is ignored).  What the reference keeps from 'START'
+                                stays: prjctd, cnstnd, boxed and the projection of x0 (errclb and active do
+                                not run again).  An nbd value outside 0..3 ends the run with
+                                'ERROR: INVALID NBD' (isave(35), info, = -6).  Edits are made in stream order:
+                                complete, or ordered on the context's stream, before the next call -- the rule
+                                that applies to g.  Sharded runs: the changed-row count (a new pointer on
+                                one rank included) is reduced over the ranks, so every rank rebuilds at the
+                                same entry.  LBFGSB_F_DEFER_LNSRCH (and option "defer_lnsrch") is turned off
+                                in such a context: a deferred line-search set-up would run with the bounds of
+                                the next call, where the reference uses those of its own; the set-up then
+                                runs in its own call -- the same numbers, one host sync more.  Only the
+                                device-pointer forms follow edits; the host form keeps the default.  Not
+                                needed by a caller that announces its edits (lbfgsb_hip_bounds_changed). */
 };
 
 /* -------------------------------------------------------------------------
@@ -188,7 +210,8 @@ int lbfgsb_hip_comm_init_host(lbfgsb_hip_ctx *ctx, lbfgsb_allreduce_fn ar,
  * arrays are compared with the snapshot bit for bit, and a difference ends the run with
  * task = 'ERROR: BOUNDS CHANGED DURING RUN' (isave(35), info, = -10).  Passing OTHER array pointers than at
  * START is allowed: the constants / tables are dropped and the arrays are streamed from then on.  A caller that
- * has to change bounds starts a new run (task='START').
+ * has to change bounds during a run creates the context with LBFGSB_F_FOLLOW_BOUNDS, or announces each edit
+ * (lbfgsb_hip_bounds_changed), or starts a new run (task='START').
  * ------------------------------------------------------------------------- */
 int lbfgsb_hip_setulb_dev(lbfgsb_hip_ctx *ctx, void *x, const void *l, const void *u,
                           const int32_t *nbd, double *f, void *g, double factr, double pgtol,
@@ -552,6 +575,15 @@ int lbfgsb_hip_set_option(lbfgsb_hip_ctx *ctx, const char *name, double value);
  * off (any of the three for the dictionary).  Options "uniform_bounds" = 0 / "dict_bounds" = 0
  * (lbfgsb_hip_set_option, before START) disable the detection / the dictionary. */
 int lbfgsb_hip_uniform_bounds(lbfgsb_hip_ctx *ctx, int32_t *mask);
+
+/* Announce an edit of l, u or nbd made since the last call (with or without LBFGSB_F_FOLLOW_BOUNDS): the next
+ * entry rebuilds the snapshot without comparing, and continues as LBFGSB_F_FOLLOW_BOUNDS does on a difference.
+ * Costs nothing unless it is called.  Sharded runs without the flag: every rank announces, before the same call
+ * (with the flag an announcement on some ranks is enough: it rides in the reduced count).  Refused
+ * (LBFGSB_E_STATE) at an 'FG_LNSRCH' return whose line-search set-up is deferred (LBFGSB_F_DEFER_LNSRCH): that
+ * set-up would meet the new bounds where the reference used the old ones; edit at a 'NEW_X' return instead.
+ * Without the flag an edit that is NOT announced is still reported by the "bounds_check" comparison. */
+int lbfgsb_hip_bounds_changed(lbfgsb_hip_ctx *ctx);
 
 /* Profiling clocks, counters and bare-kernel timing doors (bench.py, profiles/scripts, tests) are declared in
  * lbfgsb_hip_debug.h: measurement instruments of the same library, not part of the drop-in surface. */

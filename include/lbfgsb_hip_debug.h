@@ -43,6 +43,9 @@ int lbfgsb_hip_stats(lbfgsb_hip_ctx *ctx, int64_t *launches, int64_t *syncs,
  * sync: no iwhere entry had changed since the previous freev (the update pass counts the entries it
  * changes, the walk knows the rows it fixes), so nobody entered or left the free set */
 int lbfgsb_hip_freev_skipped(lbfgsb_hip_ctx *ctx, int64_t *count);
+/* LBFGSB_F_FOLLOW_BOUNDS / lbfgsb_hip_bounds_changed: comparison passes run, differences found (pointer changes
+ * included), snapshot rebuilds (differences and announcements).  Any pointer may be NULL. */
+int lbfgsb_hip_bounds_stats(lbfgsb_hip_ctx *ctx, int64_t *checks, int64_t *changes, int64_t *rebuilds);
 
 /* several ranks: collectives issued so far (all-gathers of partial sums, of breakpoint records, of
  * halo values) and the bytes THIS rank contributed to them */

@@ -67,6 +67,8 @@ PROTOTYPES = {
     "lbfgsb_hip_set_option": (C.c_int, [_vp, _cp, C.c_double]),
     "lbfgsb_hip_comm_stats": (C.c_int, [_vp, _vp, _vp]),
     "lbfgsb_hip_uniform_bounds": (C.c_int, [_vp, _vp]),
+    "lbfgsb_hip_bounds_changed": (C.c_int, [_vp]),
+    "lbfgsb_hip_bounds_stats": (C.c_int, [_vp, _vp, _vp, _vp]),
     "lbfgsb_hip_freev_skipped": (C.c_int, [_vp, _vp]),
     "lbfgsb_hip_skip_stats": (C.c_int, [_vp, _vp]),
     "lbfgsb_hip_refresh_count": (C.c_int, [_vp, _vp]),
@@ -96,6 +98,7 @@ F_PARALLEL_GCP = 8
 F_EXACT_TIES = 16      # accepted and ignored: the default since round 3
 F_INDEX_TIES = 32      # opt-out: equal breakpoints in variable order, no heap-order replay
 F_DEFER_LNSRCH = 64    # the line-search set-up's sums travel with the next call's fetch (same-stream objective)
+F_FOLLOW_BOUNDS = 128  # every entry compares l, u, nbd with the snapshot and follows an edit, as the reference does
 
 
 class LbfgsbError(RuntimeError):

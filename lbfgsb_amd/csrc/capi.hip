@@ -409,6 +409,21 @@ int lbfgsb_hip_uniform_bounds(lbfgsb_hip_ctx *ctx, int32_t *mask) {
   return 0;
 }
 
+int lbfgsb_hip_bounds_changed(lbfgsb_hip_ctx *ctx) {
+  if (!ctx) return fail(LBFGSB_E_ARG, "ctx == NULL");
+  return ctx->bounds_changed();
+}
+
+int lbfgsb_hip_bounds_stats(lbfgsb_hip_ctx *ctx, int64_t *checks, int64_t *changes, int64_t *rebuilds) {
+  if (!ctx) return fail(LBFGSB_E_ARG, "ctx == NULL");
+  int64_t a = 0, b = 0, c = 0;
+  ctx->bounds_stats(a, b, c);
+  if (checks) *checks = a;
+  if (changes) *changes = b;
+  if (rebuilds) *rebuilds = c;
+  return 0;
+}
+
 int lbfgsb_hip_path_counts(lbfgsb_hip_ctx *ctx, int64_t *closed_form, int64_t *three_pass,
                            int64_t *handed_windows) {
   if (!ctx) return fail(LBFGSB_E_ARG, "ctx == NULL");

@@ -426,6 +426,12 @@ void launch_nbd_pack_dict(Queue &q, int64_t n, const int32_t *nbd, const T *l, c
 template <typename T>
 void launch_bounds_verify(Queue &q, int64_t n, const T *l, const T *u, const int32_t *nbd, const nb_t *code,
                           int ub, const BoundTables &tb);
+// LBFGSB_F_FOLLOW_BOUNDS (k_bounds.hip): the caller's l, u, nbd against the snapshot, with l_snap / u_snap
+// standing in for the arrays the passes stream; force is added once to [0].
+// res: sum [0] = rows that differ (+ force), [1] = rows with nbd outside 0..3
+template <typename T>
+void launch_bounds_follow(Queue &q, int64_t n, const T *l, const T *u, const int32_t *nbd, const T *l_snap,
+                          const T *u_snap, const nb_t *code, int ub, const BoundTables &tb, int force);
 // two copies of (l, u, nbd) against each other, bit for bit.  res: sum [0] = rows that differ
 template <typename T>
 void launch_bounds_same(Queue &q, int64_t n, const T *l0, const T *u0, const int32_t *nb0, const T *l1,

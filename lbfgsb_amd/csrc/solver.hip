@@ -81,6 +81,20 @@ class Solver final : public lbfgsb_hip_ctx {
   const T *lk(const T *l) const { return (ub_mask & 1) ? (const T *)ub_buf : l; }
   const T *uk(const T *u) const { return (ub_mask & 2) ? (const T *)(ub_buf + 64) : u; }
   const lbk::nb_t *nbk() const { return (ub_mask & 4) ? (const lbk::nb_t *)(ub_buf + 128) : nbd8; }
+  // ---- bounds that the caller edits during a run (LBFGSB_F_FOLLOW_BOUNDS, lbfgsb_hip_bounds_changed) ----
+  //      Every entry after START compares l, u, nbd with the snapshot above (bounds_follow, k_bounds.hip; with the
+  //      flag, l_snap / u_snap stand in for the arrays the passes stream); an announcement skips the comparison.
+  //      On a difference the snapshot is rebuilt by START's own analysis (analyze_bounds), and the products an
+  //      earlier call computed ahead of time from the old bounds are dropped (bnd_edit, drop_bound_products).
+  //      What the reference keeps from START -- prjctd, cnstnd, boxed, the projected x0 -- stays. ----
+  bool follow_on = false;     // LBFGSB_F_FOLLOW_BOUNDS
+  bool bnd_announced = false; // lbfgsb_hip_bounds_changed: the next entry rebuilds without comparing
+  bool snap_valid = false;    // l_snap / u_snap / the pointers below describe the arrays of this run
+  bool bnd_edit = false;      // this call's bounds differ from the last call's: drop what was computed ahead
+  T *l_snap = nullptr, *u_snap = nullptr;
+  const void *fb_l = nullptr, *fb_u = nullptr;
+  const int32_t *fb_nbd = nullptr;
+  int64_t nbf_checks = 0, nbf_changes = 0, nbf_rebuilds = 0;
   lbk::iw_t *iwhere = nullptr;  // one byte per row (the reference's int32 only in export/import)
   int32_t *index = nullptr, *indx2 = nullptr, *scan_tmp = nullptr;
   int8_t *wasfree = nullptr, *prevfree = nullptr;
@@ -158,7 +172,7 @@ class Solver final : public lbfgsb_hip_ctx {
         F(q.d_part_alt[0]), F(q.d_part_alt[1]), F(q.d_fin_count), F(d_fcount), F(wide_rows),
         F(d_fix), F(pg_buf), F(pg_tmp), F(sp_keys), F(sp_idx), F(sp_count), F(sp_msg), F(sp_msg_all), F(d_res_all),
         F(ub_buf), F(mg_keys[0]), F(mg_keys[1]), F(mg_vals[0]), F(mg_vals[1]), F(mg_tmp), F(d_merged);
-    F(hx), F(hg), F(hl), F(hu), F(hnbd);
+    F(hx), F(hg), F(hl), F(hu), F(hnbd), F(l_snap), F(u_snap);
     auto H = [](auto *&p) {
       if (p) (void)hipHostFree(p);
       p = nullptr;
@@ -198,7 +212,10 @@ class Solver final : public lbfgsb_hip_ctx {
       own_stream = true;
     }
     q.stream = stream;
-    defer_on = (flags & LBFGSB_F_DEFER_LNSRCH) != 0;
+    follow_on = (flags & LBFGSB_F_FOLLOW_BOUNDS) != 0;
+    // (a deferred line-search set-up runs in the call after the one the reference runs it in, with that call's
+    //  bounds: under the flag it runs in its own call -- the same numbers, bit for bit, one host sync more)
+    defer_on = (flags & LBFGSB_F_DEFER_LNSRCH) != 0 && !follow_on;
     ld = ((n + lbk::CW_TILE - 1) / lbk::CW_TILE) * lbk::CW_TILE;  // (whole layout tiles)
     // streamed-once data: nontemporal loads unless W fits the 256 MiB Infinity Cache
     q.nt = (size_t)2 * ld * m * sizeof(T) > ((size_t)192 << 20);
@@ -224,6 +241,11 @@ class Solver final : public lbfgsb_hip_ctx {
       HIPCHK(hipMemsetAsync(*p, 0, vb, stream));
     }
     t = t_own, r = r_own;
+    if (follow_on)
+      for (T **p : {&l_snap, &u_snap}) {
+        HIPCHK(hipMalloc(p, vb));
+        HIPCHK(hipMemsetAsync(*p, 0, vb, stream));
+      }
     HIPCHK(hipMalloc(&iwhere, (size_t)(n + 32) * sizeof(lbk::iw_t)));
     HIPCHK(hipMalloc(&nbd8, (size_t)(n + 32) * sizeof(lbk::nb_t)));
     HIPCHK(hipMemsetAsync(iwhere, 0, (size_t)(n + 32) * sizeof(lbk::iw_t), stream));
@@ -530,7 +552,7 @@ class Solver final : public lbfgsb_hip_ctx {
       }
       if (cw_hold > 0) {
         cw_hold--;
-        return;
+        if (!(cw_packed && cw_stale > 0)) return;  // (a packed layout that went stale is re-sorted all the same)
       }
       // (a W that lives in the Infinity Cache gains nothing from fewer HBM bytes: n = 1e6, m = 10 lost 2.5 %)
       const bool big = cw_min_rows >= 0 ? n >= cw_min_rows : (size_t)2 * ld * m * sizeof(T) > ((size_t)192 << 20);
@@ -665,6 +687,151 @@ class Solver final : public lbfgsb_hip_ctx {
     return 0;
   }
 
+  // the arrays the passes stream, as they are now (LBFGSB_F_FOLLOW_BOUNDS)
+  int snap_copy(const T *l, const T *u, const int32_t *nbd) {
+    HIPCHK(hipMemcpyAsync(l_snap, l, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(u_snap, u, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    fb_l = l, fb_u = u, fb_nbd = nbd;
+    snap_valid = true;
+    return 0;
+  }
+  // The top of every entry after START: compare (flag) or take the announcement, rebuild on a difference.
+  // Under the flag every rank runs the comparison and its fetch, whatever it knows already (other pointers, an
+  // announcement, the first call after import_state): that knowledge rides in the sum, which is reduced over the
+  // ranks, so every rank takes the same branch and issues the same collectives.
+  // -> *bad_nbd = errclb's k for an nbd value outside 0..3 (the packed byte cannot hold it: the run ends)
+  int follow_bounds(const T *l, const T *u, const int32_t *nbd, double *f, int64_t *bad_nbd) {
+    *bad_nbd = 0;
+    bool changed = bnd_announced;
+    bnd_announced = false;
+    if (follow_on) {
+      const int force = (changed || !snap_valid || l != fb_l || u != fb_u || nbd != fb_nbd) ? 1 : 0;
+      // (a deferred built-in objective waits in d_res[0] for this call's first fetch: stay behind it)
+      const int fo_ = f_pending ? 1 : 0;
+      q.res_off = fo_;
+      lbk::launch_bounds_follow<T>(q, n, l, u, nbd, l_snap, u_snap, nbd8, ub_mask, ub_tab, force);
+      q.res_off = 0;
+      CHK(fetch(fo_ + 2, 0, 0));
+      nbf_checks++;
+      changed = h_res[fo_] != 0.0;
+      if (changed) {
+        nbf_changes++;
+        if (f_pending) f_pending = false, *f = f_scale * h_res[0];  // (the rebuild's fetches reuse d_res[0])
+      }
+    } else if (changed && f_pending) {
+      f_pending = false;
+      CHK(fetch(1, 0, 0));
+      *f = f_scale * h_res[0];
+    }
+    if (!changed) return 0;
+    nbf_rebuilds++;
+    int64_t k6 = 0, k7 = 0;
+    nbd8_src = nullptr;  // (drive packs the plain nbd bytes again unless the dictionary does)
+    CHK(analyze_bounds(l, u, nbd, k6, k7));
+    if (!ub_on) ub_l = l, ub_u = u, ub_nbd = nbd;
+    if (k6 > 0) *bad_nbd = k6;  // (k7, l > u: the reference's errclb does not run again, neither does this)
+    bnd_edit = true;
+    return 0;
+  }
+  // bound-dependent products that an earlier call computed ahead of time and the reference computes in THIS
+  // call (cauchy :617 -- the update pass's scan sums and breakpoints, freev's speculative chain, formk's new row
+  // with the pre-walk free set): dropped, the regular routes run instead.  What the reference computed in the
+  // earlier call stays (sbgnrm from its projgr, the line search's stpmx, the pending pair).
+  // The regular cauchy scan reads the newest pair from W: a pair the update left pending is stored first.
+  int drop_bound_products(const T *x, const T *g, int col, int head) {
+    if (!bnd_edit) return 0;
+    bnd_edit = false;
+    scan.ready = false, spcand.valid = false, tbrk_valid = false, nrpre.valid = false;
+    sfv.valid = false, eager.valid = false, closed_ok = false;
+    iw_dirty += 1.0;  // (iwhere as the pass left it was made with the old bounds: freev runs)
+    if (pend.on) {
+      cx = x;
+      CHK(commit_pending(g, col, head));
+    }
+    return 0;
+  }
+
+  // errclb's pass (:1601-1643) and the bound analysis behind it: uniform arrays, dictionary tables, the packed
+  // nbd byte.  START and a mid-run rebuild (follow_bounds) share it; k6 / k7 are errclb's answers.
+  int analyze_bounds(const T *l, const T *u, const int32_t *nbd, int64_t &k6, int64_t &k7) {
+    lbk::launch_errclb<T>(q, n, row0, l, u, nbd);
+    CHK(fetch(0, 0, 5));
+    // uniform bounds (this rank's rows; every rank decides for itself: only loads are affected)
+    ub_mask = 0;
+    ub_tab = lbk::BoundTables{};
+    // (errclb's answers before the probes below reuse h_res)
+    const int64_t k6_ = (int64_t)h_res[0], k7_ = (int64_t)h_res[1];
+    const bool uni_l = h_res[2] == 0.0, uni_u = h_res[3] == 0.0, uni_nb = h_res[4] == 0.0;
+    if (ub_on) {
+      T lu0[2];
+      int32_t nb0 = 0;
+      HIPCHK(hipMemcpy(&lu0[0], l, sizeof(T), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&lu0[1], u, sizeof(T), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&nb0, nbd, sizeof(int32_t), hipMemcpyDeviceToHost));
+      // (h_res[2..4] are maxima over ALL ranks: a rank whose own rows are uniform but another's
+      //  are not simply keeps streaming -- harmless)
+      for (int j = 0; j < 8; ++j) ub_tab.l[j] = (double)lu0[0], ub_tab.u[j] = (double)lu0[1];
+      ub_tab.nl = ub_tab.nu = 1, ub_tab.nb0 = nb0;
+      if (uni_l) ub_mask |= 1;
+      if (uni_u) ub_mask |= 2;
+      if (uni_nb && nb0 >= 0 && nb0 <= 3) ub_mask |= 4;
+      // few-valued l / u: build the tables by probing (every quantity reduced over the ranks: all ranks
+      // hold the same tables after the same number of passes).  Only for valid input (errclb found nothing).
+      if (dict_on && !(uni_l && uni_u) && k6_ == 0 && k7_ == 0) {
+        lbk::BoundTables tb{};
+        bool ok = true;
+        auto member = [](const double *tab, int cnt, double v) {
+          for (int j = 0; j < cnt; ++j)
+            if (std::memcmp(&tab[j], &v, sizeof(double)) == 0) return true;
+          return false;
+        };
+        for (int trip = 0; trip < 18 && ok; ++trip) {
+          lbk::launch_dict_probe<T>(q, n, l, u, tb);
+          CHK(fetch(2, 2, 0));
+          const double cl = h_res[0], cu = h_res[1], vl = h_res[2], vu = h_res[3];
+          if (cl == 0.0 && cu == 0.0) break;
+          if (trip == 17) ok = false;
+          if (cl > 0.0) {
+            if (tb.nl == 8 || member(tb.l, tb.nl, vl)) ok = false;  // a 9th value, or one that == cannot find (NaN)
+            else tb.l[tb.nl++] = vl;
+          }
+          if (cu > 0.0) {
+            if (tb.nu == 8 || member(tb.u, tb.nu, vu)) ok = false;
+            else tb.u[tb.nu++] = vu;
+          }
+        }
+        if (ok && tb.nl >= 1 && tb.nu >= 1) {
+          for (int j = tb.nl; j < 8; ++j) tb.l[j] = tb.l[0];
+          for (int j = tb.nu; j < 8; ++j) tb.u[j] = tb.u[0];
+          tb.nb0 = nb0;
+          ub_tab = tb;
+          ub_mask = 1 | 2 | lbk::UB_DICT;
+          lbk::launch_nbd_pack_dict<T>(q, n, nbd, l, u, ub_tab, nbd8);
+          nbd8_src = nbd;
+        }
+      }
+      char host[192];
+      std::memset(host, 0, sizeof host);
+      for (int k = 0; k < 8; ++k) {  // (fp64: the whole 64 bytes; fp32: the first 32 -- every lane reads from the start)
+        const T lv = (T)ub_tab.l[k], uv = (T)ub_tab.u[k];
+        std::memcpy(host + k * sizeof(T), &lv, sizeof(T));
+        std::memcpy(host + 64 + k * sizeof(T), &uv, sizeof(T));
+      }
+      if (sizeof(T) == 4 && !(ub_mask & lbk::UB_DICT))  // (uniform fp32: the value fills the buffer as before)
+        for (int k = 8; k < 16; ++k) {
+          const T lv = (T)ub_tab.l[0], uv = (T)ub_tab.u[0];
+          std::memcpy(host + k * sizeof(T), &lv, sizeof(T));
+          std::memcpy(host + 64 + k * sizeof(T), &uv, sizeof(T));
+        }
+      std::memset(host + 128, (int)(lbk::nb_t)nb0, 64);
+      HIPCHK(hipMemcpy(ub_buf, host, sizeof host, hipMemcpyHostToDevice));
+      ub_l = l, ub_u = u, ub_nbd = nbd;
+    }
+    k6 = k6_, k7 = k7_;
+    if (follow_on) CHK(snap_copy(l, u, nbd));
+    return 0;
+  }
+
   // task = 'START' (:430-507): errclb, active, the first f,g request
   int phase_start(Mainlb &L, Flow &flow) {
     MAINLB_VIEW(L);
@@ -693,84 +860,9 @@ class Solver final : public lbfgsb_hip_ctx {
     if (nglob <= 0) lbh::str60_set(task, "ERROR: N <= 0");
     if (m <= 0) lbh::str60_set(task, "ERROR: M <= 0");
     if (factr < 0.0) lbh::str60_set(task, "ERROR: FACTR < 0");
-    lbk::launch_errclb<T>(q, n, row0, l, u, nbd);
-    CHK(fetch(0, 0, 5));
+    int64_t k6 = 0, k7 = 0;
+    CHK(analyze_bounds(l, u, nbd, k6, k7));
     {
-      // uniform bounds (this rank's rows; every rank decides for itself: only loads are affected)
-      ub_mask = 0;
-      ub_tab = lbk::BoundTables{};
-      // (errclb's answers before the probes below reuse h_res)
-      const int64_t k6_ = (int64_t)h_res[0], k7_ = (int64_t)h_res[1];
-      const bool uni_l = h_res[2] == 0.0, uni_u = h_res[3] == 0.0, uni_nb = h_res[4] == 0.0;
-      if (ub_on) {
-        T lu0[2];
-        int32_t nb0 = 0;
-        HIPCHK(hipMemcpy(&lu0[0], l, sizeof(T), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&lu0[1], u, sizeof(T), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&nb0, nbd, sizeof(int32_t), hipMemcpyDeviceToHost));
-        // (h_res[2..4] are maxima over ALL ranks: a rank whose own rows are uniform but another's
-        //  are not simply keeps streaming -- harmless)
-        for (int j = 0; j < 8; ++j) ub_tab.l[j] = (double)lu0[0], ub_tab.u[j] = (double)lu0[1];
-        ub_tab.nl = ub_tab.nu = 1, ub_tab.nb0 = nb0;
-        if (uni_l) ub_mask |= 1;
-        if (uni_u) ub_mask |= 2;
-        if (uni_nb && nb0 >= 0 && nb0 <= 3) ub_mask |= 4;
-        // few-valued l / u: build the tables by probing (every quantity reduced over the ranks: all ranks
-        // hold the same tables after the same number of passes).  Only for valid input (errclb found nothing).
-        if (dict_on && !(uni_l && uni_u) && k6_ == 0 && k7_ == 0) {
-          lbk::BoundTables tb{};
-          bool ok = true;
-          auto member = [](const double *tab, int cnt, double v) {
-            for (int j = 0; j < cnt; ++j)
-              if (std::memcmp(&tab[j], &v, sizeof(double)) == 0) return true;
-            return false;
-          };
-          for (int trip = 0; trip < 18 && ok; ++trip) {
-            lbk::launch_dict_probe<T>(q, n, l, u, tb);
-            CHK(fetch(2, 2, 0));
-            const double cl = h_res[0], cu = h_res[1], vl = h_res[2], vu = h_res[3];
-            if (cl == 0.0 && cu == 0.0) break;
-            if (trip == 17) ok = false;
-            if (cl > 0.0) {
-              if (tb.nl == 8 || member(tb.l, tb.nl, vl)) ok = false;  // a 9th value, or one that == cannot find (NaN)
-              else tb.l[tb.nl++] = vl;
-            }
-            if (cu > 0.0) {
-              if (tb.nu == 8 || member(tb.u, tb.nu, vu)) ok = false;
-              else tb.u[tb.nu++] = vu;
-            }
-          }
-          if (ok && tb.nl >= 1 && tb.nu >= 1) {
-            for (int j = tb.nl; j < 8; ++j) tb.l[j] = tb.l[0];
-            for (int j = tb.nu; j < 8; ++j) tb.u[j] = tb.u[0];
-            tb.nb0 = nb0;
-            ub_tab = tb;
-            ub_mask = 1 | 2 | lbk::UB_DICT;
-            lbk::launch_nbd_pack_dict<T>(q, n, nbd, l, u, ub_tab, nbd8);
-            nbd8_src = nbd;
-          }
-        }
-        char host[192];
-        std::memset(host, 0, sizeof host);
-        for (int k = 0; k < 8; ++k) {  // (fp64: the whole 64 bytes; fp32: the first 32 -- every lane reads from the start)
-          const T lv = (T)ub_tab.l[k], uv = (T)ub_tab.u[k];
-          std::memcpy(host + k * sizeof(T), &lv, sizeof(T));
-          std::memcpy(host + 64 + k * sizeof(T), &uv, sizeof(T));
-        }
-        if (sizeof(T) == 4 && !(ub_mask & lbk::UB_DICT))  // (uniform fp32: the value fills the buffer as before)
-          for (int k = 8; k < 16; ++k) {
-            const T lv = (T)ub_tab.l[0], uv = (T)ub_tab.u[0];
-            std::memcpy(host + k * sizeof(T), &lv, sizeof(T));
-            std::memcpy(host + 64 + k * sizeof(T), &uv, sizeof(T));
-          }
-        std::memset(host + 128, (int)(lbk::nb_t)nb0, 64);
-        HIPCHK(hipMemcpy(ub_buf, host, sizeof host, hipMemcpyHostToDevice));
-        ub_l = l, ub_u = u, ub_nbd = nbd;
-      }
-      h_res[0] = (double)k6_, h_res[1] = (double)k7_;
-    }
-    {
-      const int64_t k6 = (int64_t)h_res[0], k7 = (int64_t)h_res[1];
       if (k6 > 0 || k7 > 0) {
         if (k6 > k7) {
           lbh::str60_set(task, "ERROR: INVALID NBD");
@@ -953,7 +1045,7 @@ class Solver final : public lbfgsb_hip_ctx {
       // bcheck_every-th: the reference re-reads the arrays on every call (:1270-1330, :2594-2622, :2789-2816), so
       // an edit in place would take effect there; here it ends the run with an error instead of being ignored.
       // (At a NEW_X entry nothing deferred is in flight: the fetch is this call's own.)
-      if (bcheck_every > 0 && (iter == 1 || iter % bcheck_every == 0)) {
+      if (bcheck_every > 0 && !follow_on && (iter == 1 || iter % bcheck_every == 0)) {
         lbk::launch_bounds_verify<T>(q, n, l, u, nbd, nbd8, ub_mask, ub_tab);
         CHK(fetch(1, 0, 0));
         nbounds_checks++;
@@ -1069,6 +1161,7 @@ class Solver final : public lbfgsb_hip_ctx {
 
   int phase_cauchy_freev(Mainlb &L, Flow &flow) {
     MAINLB_VIEW(L);
+    CHK(drop_bound_products(x, g, col, head));  // (bounds edited before this call: the last pass's scan is not this cauchy's)
     if (ipr >= 99) std::fprintf(rep.out, "\n\nITERATION %5d\n", iter + 1);
     iword = -1;
     ls.ready = false;
@@ -1254,6 +1347,9 @@ class Solver final : public lbfgsb_hip_ctx {
     MAINLB_VIEW(L);
     if (nfree_g == 0 || col == 0) {
       // skip the subspace minimization :648-651: the line search starts from z = xcp
+      // (freev has folded this iteration's entering and leaving rows into wasfree: a packed layout of W no
+      //  longer holds every free row in its run -- counted, so that the next cw_maybe_pack re-sorts it)
+      if (cw_packed) cw_stale += nenter_g + std::max<int64_t>(0, nglob + 1 - ileave_g);
       CHK(commit_pending(g, col, head));
       CHK(ensure_z(x, l, u, g));
     } else {
@@ -1755,7 +1851,13 @@ class Solver final : public lbfgsb_hip_ctx {
         }
       }
     }
-    if (ub_mask && !lbh::str60_eq(task, "START")) {  // other arrays than the ones START looked at
+    int64_t bad_nbd = 0;
+    bnd_edit = false;  // (what a rebuild drops is this call's business only)
+    if (lbh::str60_eq(task, "START")) {
+      bnd_announced = false, snap_valid = false;
+    } else if (follow_on || bnd_announced) {
+      CHK(follow_bounds(L.l, L.u, nbd, f, &bad_nbd));
+    } else if (ub_mask) {  // other arrays than the ones START looked at
       if (ub_mask & lbk::UB_DICT) {
         // (the code bytes were made from all three arrays: any other array ends the dictionary mode)
         if (L.l != ub_l || L.u != ub_u || nbd != ub_nbd) ub_mask = 0, nbd8_src = nullptr;
@@ -1778,6 +1880,12 @@ class Solver final : public lbfgsb_hip_ctx {
       return 0;
     }
     phase_restore(L);
+    if (bad_nbd > 0) {  // (errclb's START-time text, :1629)
+      lbh::str60_set(L.task, "ERROR: INVALID NBD");
+      L.info = -6, err_k = bad_nbd;
+      finish(L);
+      return 0;
+    }
     PHASE(phase_entry(L, flow));
     if (L.compute_pg) PHASE(phase_first_projgr(L, flow));
     for (;;) {  // main_loop :599

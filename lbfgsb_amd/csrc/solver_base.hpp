@@ -224,6 +224,8 @@ struct lbfgsb_hip_ctx {
   }
   int64_t ncoll = 0, coll_bytes = 0;  // collectives issued / bytes THIS rank contributed to them
   virtual int uniform_mask() const = 0;  // lbfgsb_hip_uniform_bounds
+  virtual int bounds_changed() = 0;       // lbfgsb_hip_bounds_changed
+  virtual void bounds_stats(int64_t &checks, int64_t &changes, int64_t &rebuilds) const = 0;
   // two device copies of (l, u, nbd) compared bit for bit -> number of rows that differ (host-pointer form)
   virtual int bounds_same(const void *l0, const void *u0, const int32_t *nb0, const void *l1, const void *u1,
                           const int32_t *nb1, double *ndiff) = 0;

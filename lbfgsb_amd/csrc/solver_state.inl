@@ -120,6 +120,7 @@
     sfv.valid = false, sfv_hot = false, eager.valid = false, spec_live_len = 0;
     nbd8_src = nullptr;
     spcand.valid = false;
+    snap_valid = false;  // (LBFGSB_F_FOLLOW_BOUNDS: the next call takes the arrays as they are)
     {
       std::vector<lbk::iw_t> h((size_t)n);
       for (int64_t i = 0; i < n; ++i) h[(size_t)i] = (lbk::iw_t)iwa[n + i];
@@ -336,6 +337,17 @@
   void defer_counts(int64_t &deferred, int64_t &reissued) const override { deferred = ndeferred, reissued = nredo; }
   const void *prev_iterate() const override { return t; }
   int uniform_mask() const override { return ub_mask; }
+  int bounds_changed() override {
+    // (a line-search set-up deferred to the next call would meet the new bounds where the reference used the old)
+    if (ls.deferred)
+      return fail(LBFGSB_E_STATE, "bounds_changed: a line-search set-up is deferred (LBFGSB_F_DEFER_LNSRCH): "
+                                  "edit bounds at a NEW_X return, or use LBFGSB_F_FOLLOW_BOUNDS");
+    bnd_announced = true;
+    return 0;
+  }
+  void bounds_stats(int64_t &checks, int64_t &changes, int64_t &rebuilds) const override {
+    checks = nbf_checks, changes = nbf_changes, rebuilds = nbf_rebuilds;
+  }
   int bounds_same(const void *l0, const void *u0, const int32_t *nb0, const void *l1, const void *u1,
                   const int32_t *nb1, double *ndiff) override {
     HIPCHK(hipSetDevice(device));

@@ -467,7 +467,11 @@
     if (k == "lean") return flag(lean_on);
     if (k == "spec_capture") return flag(spec_on);
     if (k == "exact_always") return flag(exact_always);
-    if (k == "defer_lnsrch") return flag(defer_on);
+    if (k == "defer_lnsrch") {
+      const int rc = flag(defer_on);
+      if (follow_on) defer_on = false;  // (LBFGSB_F_FOLLOW_BOUNDS: the set-up runs in its own call)
+      return rc;
+    }
     if (k == "spin") {
       const int rc = flag(spin_on);
       q.fin_publish = spin_on && !comm;

@@ -62,7 +62,7 @@ class DeviceSolver:
                  real32: bool = False, mirror_index: bool = False, device: int = 0, stream=None,
                  same_stream_objective: bool = False, parallel_gcp: bool = False,
                  exact_ties: bool = True, index_ties: bool = False, options: Optional[dict] = None,
-                 defer_lnsrch: bool = False, stream_ordered: bool = False):
+                 defer_lnsrch: bool = False, stream_ordered: bool = False, follow_bounds: bool = False):
         self.lib = load_library()
         # LBFGSB_F_DEFER_LNSRCH returns 'FG_LNSRCH' without waiting for the pass that writes the trial point
         # (it implies LBFGSB_F_NO_RETURN_SYNC): only a caller whose objective runs on the solver's OWN stream
@@ -93,6 +93,8 @@ class DeviceSolver:
         # the caller evaluates f,g on the solver's stream and re-enters with nothing in between: the
         # line-search set-up's sums ride with the next call's fetch (include/lbfgsb_hip.h)
         flags |= capi.F_DEFER_LNSRCH if defer_lnsrch else 0
+        # l, u, nbd may be edited between calls: every entry compares them with the snapshot (include/lbfgsb_hip.h)
+        flags |= capi.F_FOLLOW_BOUNDS if follow_bounds else 0
         h = C.c_void_p()
         sp = C.c_void_p(int(stream)) if stream else None
         check(self.lib.lbfgsb_hip_create(self.n, self.n_global, self.row0, self.m, flags, device,
@@ -536,6 +538,17 @@ class DeviceSolver:
         c = C.c_int32()
         check(self.lib.lbfgsb_hip_uniform_bounds(self.h, C.byref(c)))
         return int(c.value)
+
+    def bounds_changed(self):
+        """announce an edit of l, u or nbd made since the last setulb call: the next call rebuilds the snapshot
+        (lbfgsb_hip_bounds_changed; sharded runs: every rank announces)"""
+        check(self.lib.lbfgsb_hip_bounds_changed(self.h))
+
+    def bounds_stats(self):
+        """(comparison passes, differences found, snapshot rebuilds) -- lbfgsb_hip_bounds_stats"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.lib.lbfgsb_hip_bounds_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def comm_info(self):
         """(nranks, rank, kind) of the context's communicator; kind 0 none, 1 RCCL (the communicator's own
