@@ -10,10 +10,13 @@ outside the clock) until K steps are timed.  With --gpus N the n rows are sharde
 ranks (STRONG scaling: n stays 1e8) and every reduction is completed with ONE RCCL collective
 per host sync (all-gather of the <= 8m+15 partials, reduced in rank order on every rank).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n ROWS] [--m M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n ROWS] [--m M] [--full]
 
 Prints ONE JSON line (rank 0).  `value` = K / wall time of the K timed iterations
 (objective evaluations included; `iters_per_sec_setulb_only` excludes them).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints plain_line(): the contract's
+keys and what the timed leg measured on the way.  Everything else below runs only with --full, after the timed
+steps, and goes into compact_line():
 `roofline` is the DOMINANT kernel of the iteration (the one storing pass, subsm_update_kernel),
 timed live with HIP events on the solver's stream inside the timed region, its `traffic` counted in
 this run by two `rocprofv3 --pmc` child runs of this file after the timed legs (live_traffic()); the read-only pass
@@ -52,6 +55,12 @@ def parse():
                          "own parser does not mistake for one of its options)")
     ap.add_argument("--m", type=int, default=10)
     ap.add_argument("--real32", action="store_true", help="REAL32 context (BASELINE.json configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline figure: "
+                         "rooflines (back-to-back kernel timings, live PMC traffic), the in-run parity check "
+                         "against the reference's rows, the opt-in parallel GCP, the other BASELINE.json configs, "
+                         "the host-pointer form, the CPU baseline and (several ranks or --rccl-self) the "
+                         "communicator's own sync cost; the --no-* options below leave parts of that out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short legs for the other BASELINE.json configs (N=1 only anyway)")
@@ -84,8 +93,6 @@ def parse():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="skip the two rocprofv3 --pmc child runs that count the HBM bytes of the passes over W "
                          "(N=1 only; skipped by itself when this process already runs under a profiler)")
-    ap.add_argument("--pmc-child", action="store_true",
-                    help="(internal) the run rocprofv3 counts: warm-up + timed iterations, then exit")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the caller received at the last one to DIR/<name>.npy: "
                          "x.npy, g.npy (a fixed, seeded sample of %d rows when n is larger; the row numbers in "
@@ -139,8 +146,8 @@ def live_traffic(a, n_loc, timeout_s=240):
     """HBM bytes per launch of the passes over W, COUNTED IN THIS RUN: two child runs of this file under
     `rocprofv3 --pmc FETCH_SIZE --kernel-trace` and `rocprofv3 --pmc WRITE_SIZE --kernel-trace` (separate
     passes, no other trace domain, the program itself after `--`: MI355X_MICROARCH.md, HBM / rocprofv3).
-    The child (--pmc-child) runs the same workload through the same entry: START, warm-up until the memory
-    is full, a few more iterations, exit.  Corrections for gfx950 as that guide prescribes: both counters
+    The child is a plain run of this file (no --full): the same workload through the same entry, START, warm-up
+    until the memory is full, a few more iterations, exit.  Corrections for gfx950 as that guide prescribes: both counters
     are in KiB, FETCH_SIZE reports half of the bytes of a wide coalesced streaming read (x2), WRITE_SIZE is
     exact.  Launches at col = m are the ones whose counter is within 1 % of the largest seen for that kernel
     (earlier launches read fewer columns).  Returns {kernel family: bytes per launch} or raises."""
@@ -157,9 +164,8 @@ def live_traffic(a, n_loc, timeout_s=240):
         raise RuntimeError("rocprofv3 not found")
     base = tempfile.mkdtemp(prefix="lbfgsb_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--pmc-child", "--steps", "4", "--warmup",
-             str(a.warmup), "--n", str(a.n), "--m", str(a.m), "--no-cpu-baseline", "--no-other-configs",
-             "--no-live-traffic"]
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", str(a.warmup), "--n",
+             str(a.n), "--m", str(a.m)]
     child += ["--real32"] if a.real32 else []
     child += ["--classic"] if a.classic else []
     child += ["--no-compact"] if a.no_compact else []
@@ -883,6 +889,40 @@ def compact_line(out):
     return txt
 
 
+def headline(a, r, world):
+    """the contract's keys of the line from the timed leg r -- the same in a plain and in a --full run"""
+    return {"metric": "setulb iters/sec + achieved HBM GB/s on WS/WY matvec, n=1e8 m=10",
+            "value": a.steps / r["dt"], "unit": "iters/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": r["dt"] / a.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32" if a.real32 else "f64", "data": "synthetic"}
+
+
+def run_config(a, run, opts):
+    """what was timed: workload, shape, entry, context options (the same in a plain and in a --full run)"""
+    return {"workload": ("extended Rosenbrock with the drivers' box (--rosenbrock), n=%d, m=%d, %s, on-device "
+                         "objective" if a.rosenbrock else
+                         "separable bounded quadratic (SURVEY.md 8d), n=%d, m=%d, %s, "
+                         "l=-1,u=1,x0=0, on-device objective")
+                        % (run.n, run.m, "fp32 storage/fp64 accumulate" if a.real32 else "fp64"),
+            "n": run.n, "m": run.m, "rows_per_gpu": run.n_loc, "parallelism": "rows/%d" % run.world,
+            "collective": run.collective,
+            "entry": ("lbfgsb_hip_setulb_dev_pp (ping-pong iterate buffers)" if run.pp
+                      else "lbfgsb_hip_setulb_dev"),
+            "options": opts, "defer_lnsrch": not a.no_defer}
+
+
+def plain_line(a, r, run, opts):
+    """The line of a plain run: headline(), run_config() and what the timed leg measured on the way -- no kernel
+    timing, check, leg or baseline that takes a run of its own (those are --full's, compact_line())."""
+    st0, st1 = r["st0"], r["st1"]
+    line = dict(headline(a, r, run.world), full=False, ms_per_step_median=r["step_ms_median"],
+                ms_per_step_max=r["step_ms_max"], iters_per_sec_setulb_only=a.steps / r["dt_setulb"],
+                warmup_run=r["warm_done"], runs_restarted=r["restarts"], first_iteration_s=r["first_iter_s"],
+                first_iteration_nseg=r["nseg_first"], host_syncs_per_iter=(st1["syncs"] - st0["syncs"]) / a.steps,
+                config=run_config(a, run, opts))
+    return json.dumps(_r(line), separators=(",", ":"))
+
+
 def emit(out):
     """detail -> bench_detail.json (+ stderr), then the compact line as the LAST line of stdout"""
     detail = json.dumps(out)
@@ -939,9 +979,9 @@ def main():
     run = Run(torch, dist, lbfgsb_amd, a, n=n, m=m, real32=a.real32, kind=1 if a.rosenbrock else 0, world=world,
               rank=rank, local_rank=local_rank, rccl_self=a.rccl_self, opts=opts)
     sol, n_loc = run.sol, run.n_loc
-    # one host sync of the iteration by itself, before the run starts (every rank: it is a collective): what each of
-    # the host_syncs_per_iter below costs on this communicator (all-gather + copy to mapped host memory + poll)
-    coll_us = sol.collective_time(1000) if (world > 1 or a.rccl_self) else None
+    # --full: one host sync of the iteration by itself, before the run starts (every rank: it is a collective): what
+    # each of the host_syncs_per_iter below costs on this communicator (all-gather + copy to mapped host memory + poll)
+    coll_us = sol.collective_time(1000) if a.full and (world > 1 or a.rccl_self) else None
     # Untimed until the memory is full (col == m): whatever --warmup says, at least m + 1
     # iterations run first, so that every timed launch streams all 2m columns of W and the
     # roofline bytes below (computed for col = m) are the bytes each timed launch really moved.
@@ -950,9 +990,13 @@ def main():
     assert a.rosenbrock or min(cols_timed) == max(cols_timed) == m, cols_timed
     if a.dump_outputs:
         dump_outputs(run, rank, a.dump_outputs)
-    if a.pmc_child:   # (the run live_traffic() counts: nothing but the iterations themselves)
+    if not a.full:    # (also the run live_traffic() counts: nothing but the iterations themselves)
+        line = plain_line(a, r, run, opts)
         run.close()
-        print(json.dumps({"pmc_child": True, "steps": a.steps, "ms_per_step": dt / a.steps * 1e3}))
+        if rank == 0:
+            print(line, flush=True)
+        if world > 1:
+            dist.destroy_process_group()
         return
     stats, st0 = r["st1"], r["st0"]
     # ---- the timed path checks itself (every NEW_X row of this leg, warm-up and timed region) ----
@@ -1097,33 +1141,13 @@ def main():
                     "rows_per_launch": n_loc, "col": col}
 
     out = {
-        "metric": "setulb iters/sec + achieved HBM GB/s on WS/WY matvec, n=1e8 m=10",
-        "value": a.steps / dt,
-        "unit": "iters/sec",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
+        **headline(a, r, world),
         "warmup_run": r["warm_done"],
         "col_min_timed": min(cols_timed),
         "col_max_timed": max(cols_timed),
-        "ms_per_step": dt / a.steps * 1e3,
         "ms_per_step_median": r["step_ms_median"],
         "ms_per_step_max": r["step_ms_max"],
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32" if a.real32 else "f64",
-        "data": "synthetic",
-        "config": {"workload": ("extended Rosenbrock with the drivers' box (--rosenbrock), n=%d, m=%d, %s, on-device "
-                                "objective" if a.rosenbrock else
-                                "separable bounded quadratic (SURVEY.md 8d), n=%d, m=%d, %s, "
-                                "l=-1,u=1,x0=0, on-device objective")
-                               % (n, m, "fp32 storage/fp64 accumulate" if a.real32 else "fp64"),
-                   "n": n, "m": m, "rows_per_gpu": n_loc, "parallelism": "rows/%d" % world,
-                   "collective": run.collective,
-                   "entry": ("lbfgsb_hip_setulb_dev_pp (ping-pong iterate buffers)" if run.pp
-                             else "lbfgsb_hip_setulb_dev"),
-                   "options": opts,
+        "config": {**run_config(a, run, opts),
                    "lnsrch_setup": ("waited for at every FG_LNSRCH return (--no-defer)" if a.no_defer else
                                     "LBFGSB_F_DEFER_LNSRCH: the objective is the library's own kernel on the "
                                     "solver's stream, so the storing pass's sums ride with the next call's fetch "
@@ -1138,7 +1162,6 @@ def main():
                    "iterations_run": run.rows[-1][0] if run.rows else 0,
                    # runs of the problem started again inside the timed region (its run converged before `steps`)
                    "runs_restarted": r["restarts"],
-                   "defer_lnsrch": not a.no_defer,
                    # option compact_w: the passes over W on the tile-local free-row layout -- [on, tile re-sorts,
                    # un-sorts, packed at the end, fraction of the rows whose W entries a pass needs (nfree / n)]
                    "compact_w": [cst[3], cst[0], cst[1], cst[2], round(wfrac, 4)],

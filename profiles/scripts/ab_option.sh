@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 O=$R/$1; OPT=$2; shift 2
 mkdir -p $O
 cd $R
-COMMON="--no-cpu-baseline --no-other-configs --no-live-traffic"
+COMMON="--full --no-cpu-baseline --no-other-configs --no-live-traffic"
 k=0
 for v in "$@"; do
   k=$((k+1))

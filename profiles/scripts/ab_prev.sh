@@ -7,7 +7,7 @@ mkdir -p $out
 for rep in 1 2; do
   for which in prev new; do
     if [ $which = prev ]; then export LBFGSB_HIP_LIBRARY=$PWD/lbfgsb_amd/liblbfgsb_hip_prev.so; else unset LBFGSB_HIP_LIBRARY; fi
-    python bench.py --no-cpu-baseline --no-other-configs --no-live-traffic "$@" > $out/${which}_$rep.json 2> $out/${which}_$rep.err || exit 1
+    python bench.py --full --no-cpu-baseline --no-other-configs --no-live-traffic "$@" > $out/${which}_$rep.json 2> $out/${which}_$rep.err || exit 1
   done
 done
 python - $out <<'P'

@@ -7,7 +7,7 @@ O=$R/${1:-gpurun_out/small}
 shift || true
 mkdir -p $O
 cd $R
-COMMON="--no-cpu-baseline --no-other-configs --no-live-traffic $*"
+COMMON="--full --no-cpu-baseline --no-other-configs --no-live-traffic $*"
 python3 bench.py --n 1000000 --steps 40 $COMMON > $O/bench_n1e6.json 2> $O/bench_n1e6.err
 python3 bench.py --rows 12500000 --rccl-self --steps 40 $COMMON > $O/bench_n125e5.json 2> $O/bench_n125e5.err
 if [ -z "$SKIP_HEADLINE" ]; then python3 bench.py --steps 20 $COMMON > $O/bench_n1e8.json 2> $O/bench_n1e8.err; fi

@@ -1,5 +1,5 @@
 for o in "" "--opt wgrid=256" "--opt wgrid=512" "--opt wgrid=1024" "--opt pipe=0" "--opt pipe=0 --opt wgrid=512" "--opt pipe=0 --opt wgrid=1536" "--opt nt=1" "--opt fold_finalize=0"; do
-  python bench.py --n 1000000 --steps 60 --no-cpu-baseline --no-other-configs --no-live-traffic $o > /tmp/o.json 2>/dev/null
+  python bench.py --n 1000000 --steps 60 --full --no-cpu-baseline --no-other-configs --no-live-traffic $o > /tmp/o.json 2>/dev/null
   python - "$o" <<'P'
 import json,sys
 d=json.loads(open('/tmp/o.json').read().strip().split('\n')[-1])

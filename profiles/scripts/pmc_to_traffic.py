@@ -1,7 +1,7 @@
 """HBM bytes per launch of the W passes from two rocprofv3 counter passes over the bench itself:
 
-   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_fetch -- python3 bench.py --steps 5 --warmup 12 --no-cpu-baseline
-   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_write -- python3 bench.py --steps 5 --warmup 12 --no-cpu-baseline
+   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_fetch -- python3 bench.py --steps 5 --warmup 12 --full --no-cpu-baseline
+   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_write -- python3 bench.py --steps 5 --warmup 12 --full --no-cpu-baseline
    python profiles/scripts/pmc_to_traffic.py FETCH.csv WRITE.csv n > profiles/w_pass_traffic.json
 
 Corrections as MI355X_MICROARCH.md (HBM / rocprofv3 section) prescribes for gfx950: both counters are

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $R
 # the ELF interpreter itself goes after `--` (never a shim script: an exec hop behind the profiler's preload)
 PY=$(python3 -c 'import sys,os;print(os.path.realpath(sys.executable))')
-ARGS="--steps 10 --warmup 12 --no-cpu-baseline --no-other-configs $*"
+ARGS="--steps 10 --warmup 12 --full --no-cpu-baseline --no-other-configs $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- "$PY" bench.py $ARGS > $O/bench_under_rocprof.json 2> $O/stats.err
 echo stats done
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- "$PY" bench.py $ARGS > $O/b_fetch.json 2> $O/fetch.err

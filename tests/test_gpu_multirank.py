@@ -273,14 +273,15 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     ranks on cuda:0 with a gloo group, LBFGSB_RCCL_LIBRARY swaps librccl for the stand-in.  Launched BARE --
     `python bench.py --gpus 2`, no launcher around it: bench.py starts torch.distributed.run itself as a child
     process (before it touches the GPU) and forwards rank 0's line and the exit code; the launched ranks take
-    the very route the driver's own `python -m torch.distributed.run ... bench.py --gpus N` takes."""
+    the very route the driver's own `python -m torch.distributed.run ... bench.py --gpus N` takes.  The scaling keys
+    asserted here (collective_us, the roofline, bench_detail.json) are measured by a --full run."""
     root = os.path.dirname(HERE)
     env = dict(os.environ, LBFGSB_BENCH_SHARE_GPU="1", LBFGSB_RCCL_LIBRARY=_fake_rccl(),
                MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "2000000", "--steps", "5",
-           "--warmup", "12", "--no-cpu-baseline"]
+           "--warmup", "12", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
