@@ -12,11 +12,12 @@ __global__ __launch_bounds__(BLOCK) void cauchy_scan_kernel(
     const int32_t *__restrict__ nbd, const T *__restrict__ g, iw_t *iwhere, T *tbrk,
     const T *__restrict__ ws, const T *__restrict__ wy, const T *__restrict__ zero, int64_t ldw,
     int m, int head, int col, double *part) {
-  constexpr int NA = 2 * MC + 5;
+  static constexpr CauchyScanSlots S{MC};
+  constexpr int NA = S.size(), NSUM = S.nsum();
   double acc[NA];
 #pragma unroll
   for (int k = 0; k < NA; ++k) acc[k] = 0.0;
-  acc[2 * MC + 4] = LB_INF;  // bkmin
+  acc[S.bkmin()] = LB_INF;
   for_rows<T, RowsPer<T, MC>::V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
     double xv[W], lv[W], uv[W], gv[W], tb[W], ng[W];
@@ -59,19 +60,19 @@ __global__ __launch_bounds__(BLOCK) void cauchy_scan_kernel(
         ng[k] = 0.0;
       } else {
         ng[k] = neggi;
-        acc[2 * MC] = acc[2 * MC] - neggi * neggi;  // f1
+        acc[S.f1()] = acc[S.f1()] - neggi * neggi;
         if (nb[k] <= 2 && nb[k] != 0 && neggi < 0.0) {
           tb[k] = tl / (-neggi);
-          acc[2 * MC + 1] += 1.0;
-          acc[2 * MC + 4] = fmin(acc[2 * MC + 4], tb[k]);
+          acc[S.nbreak()] += 1.0;
+          acc[S.bkmin()] = fmin(acc[S.bkmin()], tb[k]);
         } else if (nb[k] >= 2 && neggi > 0.0) {
           tb[k] = tu / neggi;
-          acc[2 * MC + 1] += 1.0;
-          acc[2 * MC + 4] = fmin(acc[2 * MC + 4], tb[k]);
+          acc[S.nbreak()] += 1.0;
+          acc[S.bkmin()] = fmin(acc[S.bkmin()], tb[k]);
         } else {
           tb[k] = LB_INF;
-          acc[2 * MC + 2] += 1.0;
-          if (fabs(neggi) > 0.0) acc[2 * MC + 3] += 1.0;
+          acc[S.nunb()] += 1.0;
+          if (fabs(neggi) > 0.0) acc[S.nunbnz()] += 1.0;
         }
       }
     }
@@ -80,16 +81,15 @@ __global__ __launch_bounds__(BLOCK) void cauchy_scan_kernel(
       for (int j = 0; j < MC; ++j) {
 #pragma unroll
         for (int k = 0; k < W; ++k) {
-          acc[j] += a[j][k] * ng[k];
-          acc[MC + j] += b[j][k] * ng[k];
+          acc[S.p_wy(j)] += a[j][k] * ng[k];
+          acc[S.p_ws(j)] += b[j][k] * ng[k];
         }
       }
     }
     sti<W>(iwhere + i, iw);
     st<W>(tbrk + i, tb);
   });
-  // slots [0..MC) Wy'd, [MC..2MC) Ws'd, then f1, nbreak, nunb, nunbnz (sums), bkmin (min)
-  block_reduce_store<NA>(acc, 2 * MC + 4, 1, 0, part, MAX_BLOCKS);
+  block_reduce_store<NA>(acc, NSUM, 1, 0, part, MAX_BLOCKS);
 }
 template <typename T>
 void launch_cauchy_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
@@ -105,7 +105,7 @@ void launch_cauchy_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
                                           w.zero, w.ld, w.m, head, col, q.part()));
   }
   LB_LAUNCHED(q);
-  launch_finalize(q, gr, 2 * (col == 0 ? 0 : maxc_for(col)) + 4, 1, 0);
+  launch_finalize(q, gr, CauchyScanSlots::of(col).nsum(), 1, 0);
 }
 
 

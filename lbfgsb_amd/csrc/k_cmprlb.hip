@@ -53,7 +53,8 @@ __global__ __launch_bounds__(BLOCK) void cmprlb_wtv_kernel(
     const iw_t *__restrict__ iwhere, const T *__restrict__ ws, const T *__restrict__ wy,
     const T *__restrict__ zero, int64_t ldw, int m, int head, int col, double theta, Coef cf,
     const T *pr, const T *pd, Pend pe, double *part) {
-  constexpr int NA = NEWROW ? 6 * MC : 2 * MC;
+  static constexpr CmprlbWtvSlots S{MC, NEWROW};
+  constexpr int NA = S.size();
   constexpr int V = RowsPerAcc<T, MC, NA>::V;
   double acc[NA];
 #pragma unroll
@@ -115,13 +116,13 @@ __global__ __launch_bounds__(BLOCK) void cmprlb_wtv_kernel(
       col_pair<T, MC, W, PSPEC, true>(tr.ra, tr.rb, j, col, pe, gv, aj, bj);
 #pragma unroll
       for (int k = 0; k < W; ++k) {
-        acc[j] += aj[k] * rv[k];
-        acc[MC + j] += bj[k] * rv[k];
+        acc[S.wy(j)] += aj[k] * rv[k];
+        acc[S.ws(j)] += bj[k] * rv[k];
         if constexpr (NEWROW) {
-          acc[2 * MC + j] += yf[k] * aj[k];  // temp1 (:1764)
-          acc[3 * MC + j] += sa[k] * bj[k];  // temp2 (:1769)
-          acc[4 * MC + j] += sa[k] * aj[k];  // temp3 (:1770)
-          acc[5 * MC + j] += bj[k] * yf[k];  // temp3 of the new column (:1789)
+          acc[S.nr(0, j)] += yf[k] * aj[k];  // temp1 (:1764)
+          acc[S.nr(1, j)] += sa[k] * bj[k];  // temp2 (:1769)
+          acc[S.nr(2, j)] += sa[k] * aj[k];  // temp3 (:1770)
+          acc[S.nr(3, j)] += bj[k] * yf[k];  // temp3 of the new column (:1789)
         }
       }
     }
@@ -169,7 +170,8 @@ __global__ __launch_bounds__(BLOCK) void cmprlb_wtv_pair_kernel(
     const iw_t *__restrict__ iwhere, const T *__restrict__ ws, const T *__restrict__ wy,
     int64_t ldw, int m, int head, int col, double theta, Coef cf, const T *pr,
     const T *pd, Pend pe, double *part) {
-  constexpr int H = MC / 2, G = NEWROW ? 6 : 2, NA = G * H;
+  static constexpr CmprlbWtvSlots S{MC, NEWROW};
+  constexpr int H = MC / 2, G = S.groups(), NA = G * H;  // acc: this lane's half of the columns, [group][H]
   // (fp32, MC = 32 with the new-row sums: ONE row per lane -- two rows of 64 operands next to 96 fp64 sums
   //  do not fit the register file: 340 bytes of scratch; 4-byte loads are the lesser evil)
   constexpr int V = (NEWROW && MC > 20 && sizeof(T) == 4) ? 1 : RowsPer<T, MC>::V;
@@ -279,16 +281,17 @@ __global__ __launch_bounds__(BLOCK) void cmprlb_wtv_pair_kernel(
     for (int64_t rrow = nv * V; rrow < n; ++rrow) process(rrow, WTag<1>{}, std::false_type{});
   }
   // each lane holds the sums of its half of the columns: zeros for the other half, then the ordinary
-  // fixed-order reduction over all lanes (slots in the plain kernel's layout: group * MC + column)
-  double full[G * MC];
+  // fixed-order reduction over all lanes (slots in the plain kernel's layout)
+  constexpr int NF = S.size();
+  double full[NF];
 #pragma unroll
   for (int gq = 0; gq < G; ++gq)
 #pragma unroll
     for (int jj = 0; jj < H; ++jj) {
-      full[gq * MC + jj] = hi ? 0.0 : acc[gq * H + jj];
-      full[gq * MC + H + jj] = hi ? acc[gq * H + jj] : 0.0;
+      full[S.group(gq, jj)] = hi ? 0.0 : acc[gq * H + jj];
+      full[S.group(gq, H + jj)] = hi ? acc[gq * H + jj] : 0.0;
     }
-  block_reduce_store<G * MC>(full, G * MC, 0, 0, part, MAX_BLOCKS);
+  block_reduce_store<NF>(full, NF, 0, 0, part, MAX_BLOCKS);
 }
 
 template <typename T>
@@ -372,7 +375,7 @@ void launch_cmprlb_wtv(Queue &q, int64_t n, const T *x, const T *g, double tsum,
 #undef LB_CMPRLB
 #undef LB_PAIRK
   LB_LAUNCHED(q);
-  launch_finalize(q, gr, (newrow ? 6 : 2) * mc, 0, 0);
+  launch_finalize(q, gr, CmprlbWtvSlots{mc, newrow != 0}.size(), 0, 0);
 }
 
 // =========================== explicit instantiations =========================

@@ -60,7 +60,6 @@ bool pipe_on(const Queue &q, int mc, int elem_bytes) {
   return mc == 20 || (mc == 10 && elem_bytes == 4);  // (the shapes DISPATCH_PIPE compiles)
 }
 
-int maxc_for(int col) { return col <= 5 ? 5 : (col <= 10 ? 10 : (col <= 20 ? 20 : 32)); }
 
 // =========================== finalize ======================================
 // One workgroup per output slot: fixed-order sum / min / max of the per-block partials.
@@ -417,9 +416,10 @@ __global__ __launch_bounds__(BLOCK) void wtv_kernel(int64_t n, const T *__restri
                                                     const T *__restrict__ zero, int64_t ldw, int m,
                                                     int head, int col, const T *__restrict__ v,
                                                     double *part) {
-  double acc[2 * MC];
+  static constexpr WtvSlots S{MC};
+  double acc[S.size()];
 #pragma unroll
-  for (int k = 0; k < 2 * MC; ++k) acc[k] = 0.0;
+  for (int k = 0; k < S.size(); ++k) acc[k] = 0.0;
   for_rows<T, RowsPer<T, MC>::V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
     double vv[W], a[MC][W], b[MC][W];
@@ -434,13 +434,14 @@ __global__ __launch_bounds__(BLOCK) void wtv_kernel(int64_t n, const T *__restri
     for (int j = 0; j < MC; ++j) {
 #pragma unroll
       for (int k = 0; k < W; ++k) {
-        acc[j] += a[j][k] * vv[k];
-        acc[MC + j] += b[j][k] * vv[k];
+        acc[S.wy(j)] += a[j][k] * vv[k];
+        acc[S.ws(j)] += b[j][k] * vv[k];
       }
     }
   });
-  // slots [0..MC) = Wy' v, [MC..2MC) = Ws' v; entries >= col are discarded by the host
-  block_reduce_store<2 * MC>(acc, 2 * MC, 0, 0, part, MAX_BLOCKS);
+  // (entries >= col are discarded by the host)
+  constexpr int NA = S.size();
+  block_reduce_store<NA>(acc, NA, 0, 0, part, MAX_BLOCKS);
 }
 template <typename T>
 void launch_wtv_nofinalize(Queue &q, int64_t n, WStore<T> w, int head, int col, const T *v) {
@@ -452,7 +453,7 @@ void launch_wtv_nofinalize(Queue &q, int64_t n, WStore<T> w, int head, int col, 
 template <typename T>
 void launch_wtv(Queue &q, int64_t n, WStore<T> w, int head, int col, const T *v) {
   launch_wtv_nofinalize(q, n, w, head, col, v);
-  launch_finalize(q, grid_for_w(q, n, VecOf<T>::V), 2 * maxc_for(col), 0, 0);
+  launch_finalize(q, grid_for_w(q, n, VecOf<T>::V), WtvSlots{maxc_for(col)}.size(), 0, 0);
 }
 
 

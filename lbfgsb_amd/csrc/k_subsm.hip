@@ -186,7 +186,7 @@ __global__ __launch_bounds__(BLOCK) void subsm_update_kernel(
     T *xout, int do_stpmx, Pend pe, const T *pd, T *cwy, T *cws, int ub, double *part, int pstride,
     const uint64_t *__restrict__ lmask = nullptr) {
   static_assert(!CW || (sizeof(T) == 8 && MC <= 10 && !PIPE), "compact W: fp64, MC <= 10, one trip in flight");
-  double acc[4] = {0.0, 0.0, 0.0, 1.0e10};
+  double acc[SUBSM_SIZE] = {0.0, 0.0, 0.0, 1.0e10};  // (SubsmSlot: three sums, the minimum)
   const double rtheta = 1.0 / theta;
   constexpr int V = RowsPer<T, MC>::V;
   // stores every trip issues (a lower bound: the counted wait of the pipelined loop may then wait
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(BLOCK) void subsm_update_kernel(
       // refuses the result (subspace_land).
 #pragma unroll
       for (int k = 0; k < W; ++k)
-        if (!tr.lf(k) && iw[k] <= 0) acc[0] += 1.0e30;
+        if (!tr.lf(k) && iw[k] <= 0) acc[SUBSM_IWORD] += 1.0e30;
     }
     get_cols<T, MC, W>(tr.ra, tr.rb, a, b);
     fix_pending<T, MC, W, PSPEC>(col, pe, gv, xv, a, b);
@@ -239,30 +239,30 @@ __global__ __launch_bounds__(BLOCK) void subsm_update_kernel(
         if (nb[k] != 0) {
           if (nb[k] == 1) {
             zv[k] = fmax(lv[k], xk + dk);
-            if (zv[k] == lv[k]) acc[0] += 1.0;
+            if (zv[k] == lv[k]) acc[SUBSM_IWORD] += 1.0;
           } else if (nb[k] == 2) {
             const double t1 = fmax(lv[k], xk + dk);
             zv[k] = fmin(uv[k], t1);
-            if (zv[k] == lv[k] || zv[k] == uv[k]) acc[0] += 1.0;
+            if (zv[k] == lv[k] || zv[k] == uv[k]) acc[SUBSM_IWORD] += 1.0;
           } else if (nb[k] == 3) {
             zv[k] = fmin(uv[k], xk + dk);
-            if (zv[k] == uv[k]) acc[0] += 1.0;
+            if (zv[k] == uv[k]) acc[SUBSM_IWORD] += 1.0;
           }
         } else {
           zv[k] = xk + dk;
         }
       }
       dv[k] = zv[k] - xv[k];            // mainlb :720-722
-      acc[1] = acc[1] + dv[k] * gv[k];  // dd_p (:2824-2827) == g'd (:2244)
-      acc[2] = acc[2] + dv[k] * dv[k];  // dtd (:2196)
+      acc[SUBSM_DDP] = acc[SUBSM_DDP] + dv[k] * gv[k];  // dd_p (:2824-2827) == g'd (:2244)
+      acc[SUBSM_DTD] = acc[SUBSM_DTD] + dv[k] * dv[k];  // dtd (:2196)
       if (do_stpmx && nb[k] != 0) {     // :2206-2225
         const double a1 = dv[k];
         if (a1 < 0.0 && nb[k] <= 2) {
           const double a2 = lv[k] - xv[k];
-          acc[3] = fmin(acc[3], a2 >= 0.0 ? 0.0 : a2 / a1);
+          acc[SUBSM_STPMX] = fmin(acc[SUBSM_STPMX], a2 >= 0.0 ? 0.0 : a2 / a1);
         } else if (a1 > 0.0 && nb[k] >= 2) {
           const double a2 = uv[k] - xv[k];
-          acc[3] = fmin(acc[3], a2 <= 0.0 ? 0.0 : a2 / a1);
+          acc[SUBSM_STPMX] = fmin(acc[SUBSM_STPMX], a2 <= 0.0 ? 0.0 : a2 / a1);
         }
       }
     }
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(BLOCK) void subsm_update_kernel(
     for_tiles_cw<SubsmTripCW2<T, MC, NT, PSPEC>, SubsmTripCW1<T, MC, NT, PSPEC>>(n, ctx, lmask, body);
   else
     for_rows_raw<SubsmTrip<T, MC, V, NT, PSPEC>, SubsmTrip<T, MC, 1, NT, PSPEC>, V, PIPE, NS>(n, ctx, body);
-  block_reduce_store<4>(acc, 3, 1, 0, part, pstride);
+  block_reduce_store<SUBSM_SIZE>(acc, SUBSM_NSUM, 1, 0, part, pstride);
 }
 template <typename T>
 void launch_subsm_update(Queue &q, int64_t n, double tsum, T *zout, const T *pr, T *rout, const T *l,
@@ -321,7 +321,7 @@ void launch_subsm_update(Queue &q, int64_t n, double tsum, T *zout, const T *pr,
         }
 #undef LB_SUBSM_CW
         LB_LAUNCHED(q);
-        finalize_from(q, part, pstride, gr, 3, 1, 0);
+        finalize_from(q, part, pstride, gr, SUBSM_NSUM, 1, 0);
         done = true;
       }
     }
@@ -345,7 +345,7 @@ void launch_subsm_update(Queue &q, int64_t n, double tsum, T *zout, const T *pr,
     LB_SUBSM(false);
 #undef LB_SUBSM
   LB_LAUNCHED(q);
-  finalize_from(q, part, pstride, gr, 3, 1, 0);
+  finalize_from(q, part, pstride, gr, SUBSM_NSUM, 1, 0);
 }
 
 // The Newton direction as a vector (free rows; 0 elsewhere), for the backtracking branch only.

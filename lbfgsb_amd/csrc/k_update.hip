@@ -12,7 +12,8 @@ __global__ __launch_bounds__(BLOCK) void update_pairs_kernel(
     int64_t n, const T *__restrict__ g, const T *__restrict__ r, const T *__restrict__ d,
     double stp, T *ws, T *wy, const T *__restrict__ zero, int64_t ldw, int m, int head, int nold,
     int itail, double *part) {
-  constexpr int NA = 2 * MC + 1;
+  static constexpr UpdatePairsSlots S{MC};
+  constexpr int NA = S.size();
   double acc[NA];
 #pragma unroll
   for (int k = 0; k < NA; ++k) acc[k] = 0.0;
@@ -32,21 +33,20 @@ __global__ __launch_bounds__(BLOCK) void update_pairs_kernel(
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       rv[k] = gv[k] - rv[k];                   // y = g - g_old (:813-815)
-      acc[2 * MC] = acc[2 * MC] + rv[k] * rv[k];  // rr (:816)
+      acc[S.yy()] = acc[S.yy()] + rv[k] * rv[k];  // rr (:816)
       if (stp != 1.0) dv[k] = stp * dv[k];     // dscal (:822)
     }
 #pragma unroll
     for (int j = 0; j < MC; ++j) {
 #pragma unroll
       for (int k = 0; k < W; ++k) {
-        acc[j] += dv[k] * a[j][k];        // Sy(col,j) = d . Wy(:,j) (:2335)
-        acc[MC + j] += b[j][k] * dv[k];   // Ss(j,col) = Ws(:,j) . d (:2336)
+        acc[S.sy(j)] += dv[k] * a[j][k];  // Sy(col,j) = d . Wy(:,j) (:2335)
+        acc[S.ss(j)] += b[j][k] * dv[k];  // Ss(j,col) = Ws(:,j) . d (:2336)
       }
     }
     st<W>(ws + offn + i, dv);  // :2313
     st<W>(wy + offn + i, rv);  // :2314
   });
-  // slots [0..MC) d'Wy_j, [MC..2MC) Ws_j'd, [2MC] y'y
   block_reduce_store<NA>(acc, NA, 0, 0, part, MAX_BLOCKS);
 }
 template <typename T>
@@ -58,7 +58,7 @@ void launch_update_pairs(Queue &q, int64_t n, const T *g, const T *r, const T *d
                                          q.stream, n, g, r, d, stp, w.ws, w.wy, w.zero, w.ld, w.m,
                                          head, nold, itail, q.part()));
   LB_LAUNCHED(q);
-  launch_finalize(q, gr, 2 * maxc_for(nold) + 1, 0, 0);
+  launch_finalize(q, gr, UpdatePairsSlots{maxc_for(nold)}.size(), 0, 0);
 }
 
 // =========================== matupd + cauchy scan, fused ======================
@@ -67,9 +67,7 @@ void launch_update_pairs(Queue &q, int64_t n, const T *g, const T *r, const T *d
 // the old columns are read ONCE for s'Wy_j, Ws_j's (matupd) and for p = W'd (cauchy), and
 // the new pair (s, y) is used from registers.  Per element the arithmetic is exactly that
 // of update_pairs_kernel and cauchy_scan_kernel.
-// slots: [0,MC) s'Wy_j | [MC,2MC) Ws_j's | [2MC] y'y | [2MC+1,3MC+1) Wy_j'd | [3MC+1] y'd |
-//        [3MC+2,4MC+2) Ws_j'd | [4MC+2] s'd | f1, nbreak, nunb, nunbnz | [4MC+7] g'd (unscaled d)
-//        | [4MC+8] #rows whose iwhere changed | min [4MC+9] bkmin | max [4MC+10] |proj g|
+// The result slots: UpdScanSlots (res_layout.hpp).
 // The same pass serves as the line search's evaluation at a trial point (g'd, |proj g|): run
 // speculatively there (store_pair = 0; it writes nothing but -- with store_iw -- the few iwhere
 // entries that changed), its sums ARE the matupd + cauchy-scan results if the trial is accepted.
@@ -403,9 +401,7 @@ struct UpdScanPairTripCW : CwOneRow {
 // BEFORE the breakpoint walk (the host corrects the sums for the few rows the walk fixes, from
 // the records it gathers for them anyway).  With them and the walk's own p = W'd the host has
 // W'Z r in closed form (solver.hip, subspace_closed_form), and the iteration needs no third pass
-// over W.  Extra sum slots, X = 4 MC + 9:  [X, X+MC) sum_free y Wy_j | [X+MC, ..) sum_act s Ws_j |
-// [X+2MC, ..) sum_act s Wy_j | [X+3MC, ..) sum_free Ws_j y | [X+4MC ..+4) sum_free y y,
-// sum_act s s, sum_act s y, sum_free s y   (y, s in their stored form); min and max follow.
+// over W.  The extra sum slots: UpdScanSlots::nr_vec, nr_scalar (y, s in their stored form).
 // PAIR (MC = 20 with the new-row sums): the 8 sums per column are what fills the register
 // file (175 fp64 accumulators per lane), and a kernel that large runs one wave per SIMD with a
 // single trip in flight.  Neighbouring lanes therefore SHARE the per-column accumulators: the even
@@ -424,10 +420,8 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
     int store_iw, double cand_hi, uint64_t *ckeys, uint32_t *cidx, uint32_t ccap, uint32_t *ccount,
     int ub, double *part, const uint64_t *__restrict__ lmask = nullptr) {
   static_assert(!CW || (sizeof(T) == 8 && MC <= 10 && !PIPE), "compact W: fp64, MC <= 10, one trip in flight");
-  constexpr int NX = NEWROW ? 4 * MC + 4 : 0;  // extra sums
-  constexpr int X = 4 * MC + 9;                // first extra slot
-  constexpr int NA = 4 * MC + 11 + NX;
-  constexpr int IMIN = X + NX, IMAX = X + NX + 1;  // bkmin, |proj g|
+  static constexpr UpdScanSlots S{MC, NEWROW};
+  constexpr int NA = S.size(), NSUM = S.nsum();
   // (fp32, MC = 10 with the new-row sums: 4 rows per lane after all -- the 16-byte loads are worth
   //  more than the second wave the 512 registers cost: 1.88 -> 1.65 ms at n = 1e8)
   constexpr int V = CW ? 1 : ((sizeof(T) == 4 && MC == 10 && NEWROW) ? 4 : RowsPerAcc<T, MC, NA>::V);
@@ -436,7 +430,7 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
   double acc[NA];
 #pragma unroll
   for (int k = 0; k < NA; ++k) acc[k] = 0.0;
-  acc[IMIN] = LB_INF;
+  acc[S.bkmin()] = LB_INF;
   double accp[PAIR ? 8 : 1][PAIR ? H : 1];  // PAIR: this lane's half of the columns, 8 sums each
 #pragma unroll
   for (int a = 0; a < (PAIR ? 8 : 1); ++a)
@@ -478,10 +472,10 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
       //  first trial step of a lean subsm_update_kernel pass, see Pend::impl)
       if (dimpl) dv[k] = (double)(T)(xv[k] - dv[k]);
       // ---- the line search's own sums at this trial point: g'd (:2244), |proj g| (:781) ----
-      acc[4 * MC + 7] = acc[4 * MC + 7] + gv[k] * dv[k];
-      acc[IMAX] = fmax(acc[IMAX], proj_g(xv[k], lv[k], uv[k], nb[k], gv[k]));
+      acc[S.gd()] = acc[S.gd()] + gv[k] * dv[k];
+      acc[S.pgnorm()] = fmax(acc[S.pgnorm()], proj_g(xv[k], lv[k], uv[k], nb[k], gv[k]));
       rv[k] = gv[k] - rv[k];                              // y (:813-815)
-      acc[2 * MC] = acc[2 * MC] + rv[k] * rv[k];          // rr (:816)
+      acc[S.yy()] = acc[S.yy()] + rv[k] * rv[k];          // rr (:816)
       if (stp != 1.0) dv[k] = stp * dv[k];                // s (:822)
       // ---- cauchy n-loop (:1270-1330) ----
       const double neggi = -gv[k];
@@ -501,30 +495,30 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
           if (fabs(neggi) <= 0.0) iw[k] = -3;
         }
         iw_changed = iw_changed || iw[k] != iw_old;
-        if (iw[k] != iw_old) acc[4 * MC + 8] += 1.0;
+        if (iw[k] != iw_old) acc[S.iw_changed()] += 1.0;
       }
       if (iw[k] != 0 && iw[k] != -1) {
         tb[k] = -1.0;
         ng[k] = 0.0;
       } else {
         ng[k] = neggi;
-        acc[4 * MC + 3] = acc[4 * MC + 3] - neggi * neggi;
+        acc[S.f1()] = acc[S.f1()] - neggi * neggi;
         if (nb[k] <= 2 && nb[k] != 0 && neggi < 0.0) {
           tb[k] = tl / (-neggi);
-          acc[4 * MC + 4] += 1.0;
-          acc[IMIN] = fmin(acc[IMIN], tb[k]);
+          acc[S.nbreak()] += 1.0;
+          acc[S.bkmin()] = fmin(acc[S.bkmin()], tb[k]);
         } else if (nb[k] >= 2 && neggi > 0.0) {
           tb[k] = tu / neggi;
-          acc[4 * MC + 4] += 1.0;
-          acc[IMIN] = fmin(acc[IMIN], tb[k]);
+          acc[S.nbreak()] += 1.0;
+          acc[S.bkmin()] = fmin(acc[S.bkmin()], tb[k]);
         } else {
           tb[k] = LB_INF;
-          acc[4 * MC + 5] += 1.0;
-          if (fabs(neggi) > 0.0) acc[4 * MC + 6] += 1.0;
+          acc[S.nunb()] += 1.0;
+          if (fabs(neggi) > 0.0) acc[S.nunbnz()] += 1.0;
         }
       }
-      acc[3 * MC + 1] += rv[k] * ng[k];  // new Wy column . d
-      acc[4 * MC + 2] += dv[k] * ng[k];  // new Ws column . d
+      acc[S.yd()] += rv[k] * ng[k];  // new Wy column . d
+      acc[S.sd()] += dv[k] * ng[k];  // new Ws column . d
     }
     // (columns are widened one pair at a time, where they are used: the fp32 instantiations with
     //  many accumulators cannot keep all 2 MC operands of a trip as doubles)
@@ -536,10 +530,10 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
         const bool fr = iw[k] <= 0;                                   // after the n-loop's update
         yf[k] = fr ? yst : 0.0;
         sa[k] = fr ? 0.0 : sst;
-        acc[X + 4 * MC + 0] = __builtin_fma(yf[k], yst, acc[X + 4 * MC + 0]);
-        acc[X + 4 * MC + 1] = __builtin_fma(sa[k], sst, acc[X + 4 * MC + 1]);
-        acc[X + 4 * MC + 2] = __builtin_fma(sa[k], yst, acc[X + 4 * MC + 2]);
-        acc[X + 4 * MC + 3] = __builtin_fma(fr ? sst : 0.0, yst, acc[X + 4 * MC + 3]);
+        acc[S.nr_scalar(0)] = __builtin_fma(yf[k], yst, acc[S.nr_scalar(0)]);
+        acc[S.nr_scalar(1)] = __builtin_fma(sa[k], sst, acc[S.nr_scalar(1)]);
+        acc[S.nr_scalar(2)] = __builtin_fma(sa[k], yst, acc[S.nr_scalar(2)]);
+        acc[S.nr_scalar(3)] = __builtin_fma(fr ? sst : 0.0, yst, acc[S.nr_scalar(3)]);
       }
     }
     if constexpr (std::remove_reference_t<decltype(tr)>::CW) {
@@ -611,18 +605,18 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
       raw_get_col<W, false>(tr.rb[j], (const T *)nullptr, bj);
 #pragma unroll
       for (int k = 0; k < W; ++k) {
-        acc[j] += dv[k] * aj[k];               // Sy(col,j) (:2335)
-        acc[MC + j] += bj[k] * dv[k];          // Ss(j,col) (:2336)
-        acc[2 * MC + 1 + j] += aj[k] * ng[k];  // p_j        (:1301)
-        acc[3 * MC + 2 + j] += bj[k] * ng[k];  // p_{col+j}  (:1302)
+        acc[S.sy(j)] += dv[k] * aj[k];    // Sy(col,j) (:2335)
+        acc[S.ss(j)] += bj[k] * dv[k];    // Ss(j,col) (:2336)
+        acc[S.p_wy(j)] += aj[k] * ng[k];  // p_j        (:1301)
+        acc[S.p_ws(j)] += bj[k] * ng[k];  // p_{col+j}  (:1302)
       }
       if constexpr (NEWROW) {
 #pragma unroll
         for (int k = 0; k < W; ++k) {
-          acc[X + j] = __builtin_fma(yf[k], aj[k], acc[X + j]);
-          acc[X + MC + j] = __builtin_fma(sa[k], bj[k], acc[X + MC + j]);
-          acc[X + 2 * MC + j] = __builtin_fma(sa[k], aj[k], acc[X + 2 * MC + j]);
-          acc[X + 3 * MC + j] = __builtin_fma(bj[k], yf[k], acc[X + 3 * MC + j]);
+          acc[S.nr_vec(0, j)] = __builtin_fma(yf[k], aj[k], acc[S.nr_vec(0, j)]);
+          acc[S.nr_vec(1, j)] = __builtin_fma(sa[k], bj[k], acc[S.nr_vec(1, j)]);
+          acc[S.nr_vec(2, j)] = __builtin_fma(sa[k], aj[k], acc[S.nr_vec(2, j)]);
+          acc[S.nr_vec(3, j)] = __builtin_fma(bj[k], yf[k], acc[S.nr_vec(3, j)]);
         }
       }
     }
@@ -673,21 +667,24 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
     for_rows_raw<TripV, Trip1, V, PIPE, 0>(n, ctx, body);
   if constexpr (PAIR) {
     // each lane holds the sums of its half of the columns: zeros for the other half, then the
-    // ordinary fixed-order reduction over all lanes
+    // ordinary fixed-order reduction over all lanes.  (The sections' first slots as constants of their own: with
+    // S.sy(jj), ... in the loop this kernel comes out with another register allocation.)
+    constexpr int F0 = S.sy(0), F1 = S.ss(0), F2 = S.p_wy(0), F3 = S.p_ws(0);
+    constexpr int F4 = S.nr_vec(0, 0), F5 = S.nr_vec(1, 0), F6 = S.nr_vec(2, 0), F7 = S.nr_vec(3, 0);
 #pragma unroll
     for (int jj = 0; jj < H; ++jj) {
       const double z = 0.0;
-      acc[jj] = hi ? z : accp[0][jj], acc[H + jj] = hi ? accp[0][jj] : z;
-      acc[MC + jj] = hi ? z : accp[1][jj], acc[MC + H + jj] = hi ? accp[1][jj] : z;
-      acc[2 * MC + 1 + jj] = hi ? z : accp[2][jj], acc[2 * MC + 1 + H + jj] = hi ? accp[2][jj] : z;
-      acc[3 * MC + 2 + jj] = hi ? z : accp[3][jj], acc[3 * MC + 2 + H + jj] = hi ? accp[3][jj] : z;
-      acc[X + jj] = hi ? z : accp[4][jj], acc[X + H + jj] = hi ? accp[4][jj] : z;
-      acc[X + MC + jj] = hi ? z : accp[5][jj], acc[X + MC + H + jj] = hi ? accp[5][jj] : z;
-      acc[X + 2 * MC + jj] = hi ? z : accp[6][jj], acc[X + 2 * MC + H + jj] = hi ? accp[6][jj] : z;
-      acc[X + 3 * MC + jj] = hi ? z : accp[7][jj], acc[X + 3 * MC + H + jj] = hi ? accp[7][jj] : z;
+      acc[F0 + jj] = hi ? z : accp[0][jj], acc[F0 + H + jj] = hi ? accp[0][jj] : z;
+      acc[F1 + jj] = hi ? z : accp[1][jj], acc[F1 + H + jj] = hi ? accp[1][jj] : z;
+      acc[F2 + jj] = hi ? z : accp[2][jj], acc[F2 + H + jj] = hi ? accp[2][jj] : z;
+      acc[F3 + jj] = hi ? z : accp[3][jj], acc[F3 + H + jj] = hi ? accp[3][jj] : z;
+      acc[F4 + jj] = hi ? z : accp[4][jj], acc[F4 + H + jj] = hi ? accp[4][jj] : z;
+      acc[F5 + jj] = hi ? z : accp[5][jj], acc[F5 + H + jj] = hi ? accp[5][jj] : z;
+      acc[F6 + jj] = hi ? z : accp[6][jj], acc[F6 + H + jj] = hi ? accp[6][jj] : z;
+      acc[F7 + jj] = hi ? z : accp[7][jj], acc[F7 + H + jj] = hi ? accp[7][jj] : z;
     }
   }
-  block_reduce_store<NA>(acc, X + NX, 1, 1, part, MAX_BLOCKS);
+  block_reduce_store<NA>(acc, NSUM, 1, 1, part, MAX_BLOCKS);
 }
 // ---- more than 20 old pairs with formk's new-row sums: the split pass ----
 // Eight sums per column pair are 256 fp64 accumulators at MC = 32 -- no sharing between two lanes brings that
@@ -704,35 +701,31 @@ struct SplitPlan {
   int nparts, mo;
   int src[SPLIT_MAXPARTS], j0[SPLIT_MAXPARTS], cnt[SPLIT_MAXPARTS], mc[SPLIT_MAXPARTS];
 };
-__device__ __forceinline__ int split_src(int k, const SplitPlan &P) {
-  const int MO = P.mo, XO = 4 * MO + 9, NXO = 4 * MO + 4;
-  const int sa = P.src[0], ma = P.mc[0], xa = 4 * ma + 9;
-  // section `sec` (its offset as a function of the part's capacity mi) of logical column j
-  auto colmap = [&](int j, int mul, int add, int xmul) {
-    for (int p = 0; p < P.nparts; ++p)
-      if (j >= P.j0[p] && j < P.j0[p] + P.cnt[p]) {
-        const int mi = P.mc[p];
-        return P.src[p] + (xmul >= 0 ? 4 * mi + 9 + xmul * mi : mul * mi + add) + (j - P.j0[p]);
-      }
-    return -1;
-  };
-  if (k < MO) return colmap(k, 0, 0, -1);                            // Sy(col, .)
-  if (k < 2 * MO) return colmap(k - MO, 1, 0, -1);                   // Ss(., col)
-  if (k == 2 * MO) return sa + 2 * ma;                               // y'y
-  if (k < 3 * MO + 1) return colmap(k - (2 * MO + 1), 2, 1, -1);     // p (Wy half)
-  if (k == 3 * MO + 1) return sa + 3 * ma + 1;
-  if (k < 4 * MO + 2) return colmap(k - (3 * MO + 2), 3, 2, -1);     // p (Ws half)
-  if (k < XO) return sa + 4 * ma + 2 + (k - (4 * MO + 2));  // new Ws column . d, f1, counts, g'd, #iwhere changed
-  const int k2 = k - XO;
-  if (k2 < 4 * MO) return colmap(k2 % MO, 0, 0, k2 / MO);            // the four new-row vectors
-  if (k2 < NXO) return sa + xa + 4 * ma + (k2 - 4 * MO);             // their four scalars
-  return sa + xa + 4 * ma + 4 + (k2 - NXO);                          // bkmin, |proj g|
-}
+// For each named section of the merged layout: column j from the part that owns j (zero for the unroll slots
+// behind the last pair), the slots that do not depend on the columns from part 0.
 __global__ __launch_bounds__(BLOCK) void update_split_merge_kernel(double *res, SplitPlan P, int dst) {
-  const int NO = 8 * P.mo + 15;
-  for (int k = threadIdx.x; k < NO; k += BLOCK) {
-    const int s = split_src(k, P);
-    res[dst + k] = s >= 0 ? res[s] : 0.0;
+  const UpdScanSlots O{P.mo, true}, A{P.mc[0], true};
+  double *out = res + dst;
+  for (int j = threadIdx.x; j < O.mc; j += BLOCK) {
+    int p = 0;
+    while (p < P.nparts && j >= P.j0[p] + P.cnt[p]) ++p;
+    const bool live = p < P.nparts;
+    const UpdScanSlots I{live ? P.mc[p] : 0, true};
+    const double *in = res + (live ? P.src[p] : 0);
+    const int c = live ? j - P.j0[p] : 0;
+    out[O.sy(j)] = live ? in[I.sy(c)] : 0.0;
+    out[O.ss(j)] = live ? in[I.ss(c)] : 0.0;
+    out[O.p_wy(j)] = live ? in[I.p_wy(c)] : 0.0;
+    out[O.p_ws(j)] = live ? in[I.p_ws(c)] : 0.0;
+    for (int k = 0; k < 4; ++k) out[O.nr_vec(k, j)] = live ? in[I.nr_vec(k, c)] : 0.0;
+  }
+  if (threadIdx.x == BLOCK - 1) {
+    const double *a = res + P.src[0];
+    out[O.yy()] = a[A.yy()], out[O.yd()] = a[A.yd()], out[O.sd()] = a[A.sd()];
+    out[O.f1()] = a[A.f1()], out[O.nbreak()] = a[A.nbreak()], out[O.nunb()] = a[A.nunb()];
+    out[O.nunbnz()] = a[A.nunbnz()], out[O.gd()] = a[A.gd()], out[O.iw_changed()] = a[A.iw_changed()];
+    for (int k = 0; k < 4; ++k) out[O.nr_scalar(k)] = a[A.nr_scalar(k)];
+    out[O.bkmin()] = a[A.bkmin()], out[O.pgnorm()] = a[A.pgnorm()];
   }
 }
 
@@ -773,7 +766,7 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
     bool done = false;
     if constexpr (sizeof(T) == 8) {
       if (nold <= 10) {
-        const bool nrw = update_scan_extra(nold, newrow) != 0;
+        const bool nrw = newrow != 0;
 #define LB_UPDSCAN_CW(MCV, NTV, NRV)                                                                   \
   {                                                                                                    \
     gr = grid_for_w(q, n, VecOf<T>::V, (const void *)&update_scan_kernel<T, MCV, NTV, false, NRV, false, true>); \
@@ -824,7 +817,7 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
         }
 #undef LB_UPDSCAN_CW
         LB_LAUNCHED(q);
-        launch_finalize(q, nblocks >= 0 ? nblocks : gr, 4 * maxc_for(nold) + 9 + update_scan_extra(nold, newrow), 1, 1);
+        launch_finalize(q, nblocks >= 0 ? nblocks : gr, UpdScanSlots{maxc_for(nold), nrw}.nsum(), 1, 1);
         done = true;
       }
     }
@@ -857,11 +850,11 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
   // Tune::pair = 0: off; 1: on, one trip in flight; 2: two trips
   const int pair_mode = q.tune.pair;
   int nblocks = 0;
-  if (update_scan_extra(nold, newrow) && mc == 20 && pair_mode > 0) {
+  if (newrow && mc == 20 && pair_mode > 0) {
     constexpr int MC = 20;
     gr = grid_for_w(q, n, VecOf<T>::V, (const void *)&update_scan_kernel<T, MC, true, true, true, true>);
     nblocks = gr;
-    constexpr int VP = RowsPerAcc<T, MC, 4 * MC + 11 + 4 * MC + 4>::V;
+    constexpr int VP = RowsPerAcc<T, MC, UpdScanSlots{MC, true}.size()>::V;
     const int64_t n_main = n / (2 * VP) * (2 * VP), n_rest = n - n_main;
 #define LB_PAIR(NTV, PIPEV)                                                                          \
   hipLaunchKernelGGL((update_scan_kernel<T, MC, NTV, PIPEV, true, true>), dim3(gr), dim3(BLOCK), 0,  \
@@ -887,7 +880,7 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
       nblocks = n_main > 0 ? gr + 1 : 1;
       LB_LAUNCHED(q);
     }
-  } else if (update_scan_extra(nold, newrow)) {
+  } else if (newrow) {
     LB_UPDSCAN(true);
     nblocks = gr;
   } else {
@@ -896,7 +889,7 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
   }
 #undef LB_UPDSCAN
   LB_LAUNCHED(q);
-  launch_finalize(q, nblocks, 4 * mc + 9 + update_scan_extra(nold, newrow), 1, 1);
+  launch_finalize(q, nblocks, UpdScanSlots{mc, newrow != 0}.nsum(), 1, 1);
 }
 
 // =========================== explicit instantiations =========================

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(BLOCK) void tile_axpy_fused_kernel(int64_t n, const
                                                                 const iw_t *__restrict__ iwhere, T *out, WideTail<T> wt,
                                                                 double *part) {
   constexpr int G = 8;
-  double red[4] = {0.0, 0.0, 0.0, 1.0e10};
+  double red[SUBSM_SIZE] = {0.0, 0.0, 0.0, 1.0e10};  // (SubsmSlot: three sums, the minimum)
   const double rtheta = 1.0 / wt.theta;
   for_rows<T, VecOf<T>::V>(n, [&](int64_t i, auto wtag) {
     constexpr int W = decltype(wtag)::value;
@@ -147,14 +147,14 @@ __global__ __launch_bounds__(BLOCK) void tile_axpy_fused_kernel(int64_t n, const
           if (nbk[k] != 0) {
             if (nbk[k] == 1) {
               zv[k] = fmax(lv[k], xk + dk);
-              if (zv[k] == lv[k]) red[0] += 1.0;
+              if (zv[k] == lv[k]) red[SUBSM_IWORD] += 1.0;
             } else if (nbk[k] == 2) {
               const double t1 = fmax(lv[k], xk + dk);
               zv[k] = fmin(uv[k], t1);
-              if (zv[k] == lv[k] || zv[k] == uv[k]) red[0] += 1.0;
+              if (zv[k] == lv[k] || zv[k] == uv[k]) red[SUBSM_IWORD] += 1.0;
             } else if (nbk[k] == 3) {
               zv[k] = fmin(uv[k], xk + dk);
-              if (zv[k] == uv[k]) red[0] += 1.0;
+              if (zv[k] == uv[k]) red[SUBSM_IWORD] += 1.0;
             }
           } else {
             zv[k] = xk + dk;
@@ -162,16 +162,16 @@ __global__ __launch_bounds__(BLOCK) void tile_axpy_fused_kernel(int64_t n, const
           zv[k] = (double)(T)zv[k];
         }
         dv[k] = zv[k] - xv[k];              // mainlb :720-722 (lnsrlb_begin_kernel)
-        red[1] = red[1] + dv[k] * gv[k];    // dd_p (:2824-2827) == g'd (:2244)
-        red[2] = red[2] + dv[k] * dv[k];    // dtd (:2196)
+        red[SUBSM_DDP] = red[SUBSM_DDP] + dv[k] * gv[k];    // dd_p (:2824-2827) == g'd (:2244)
+        red[SUBSM_DTD] = red[SUBSM_DTD] + dv[k] * dv[k];    // dtd (:2196)
         if (wt.do_stpmx && nbk[k] != 0) {   // :2206-2225
           const double a1 = dv[k];
           if (a1 < 0.0 && nbk[k] <= 2) {
             const double a2 = lv[k] - xv[k];
-            red[3] = fmin(red[3], a2 >= 0.0 ? 0.0 : a2 / a1);
+            red[SUBSM_STPMX] = fmin(red[SUBSM_STPMX], a2 >= 0.0 ? 0.0 : a2 / a1);
           } else if (a1 > 0.0 && nbk[k] >= 2) {
             const double a2 = uv[k] - xv[k];
-            red[3] = fmin(red[3], a2 <= 0.0 ? 0.0 : a2 / a1);
+            red[SUBSM_STPMX] = fmin(red[SUBSM_STPMX], a2 <= 0.0 ? 0.0 : a2 / a1);
           }
         }
       }
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(BLOCK) void tile_axpy_fused_kernel(int64_t n, const
       if (wt.xout) st<W>(wt.xout + i, zv);  // the first trial point x = z (:2265); may alias wt.x (row read above)
     }
   });
-  if constexpr (LAST) block_reduce_store<4>(red, 3, 1, 0, part, MAX_BLOCKS);
+  if constexpr (LAST) block_reduce_store<SUBSM_SIZE>(red, SUBSM_NSUM, 1, 0, part, MAX_BLOCKS);
 }
 template <typename T>
 void launch_tile_axpy_fused(Queue &q, int64_t n, WStore<T> w, int head, int tc, const Coef &cf, const iw_t *iwhere,
@@ -204,7 +204,7 @@ void launch_tile_axpy_fused(Queue &q, int64_t n, WStore<T> w, int head, int tc, 
   }
 #undef LB_TAF
   LB_LAUNCHED(q);
-  if (last) launch_finalize(q, gr, 3, 1, 0);
+  if (last) launch_finalize(q, gr, SUBSM_NSUM, 1, 0);
 }
 
 // The r pass in one launch (kernels.hpp, launch_wide_r_pass): tile_axpy_fused_kernel<FIRST, LAST> over all col
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(BLOCK) void wide_r_pass_kernel(int64_t n, const T *
                                                             Pend pe, const T *pr, const T *pd, T *cwy, T *cws,
                                                             double *part) {
   constexpr int G = 8;
-  double red[4] = {0.0, 0.0, 0.0, 1.0e10};
+  double red[SUBSM_SIZE] = {0.0, 0.0, 0.0, 1.0e10};  // (SubsmSlot: three sums, the minimum)
   const double rtheta = 1.0 / wt.theta;
   const int jp = pe.on ? col - 1 : -1;  // the pending column
   __shared__ T dict[16];
@@ -285,14 +285,14 @@ __global__ __launch_bounds__(BLOCK) void wide_r_pass_kernel(int64_t n, const T *
         if (nbk[k] != 0) {
           if (nbk[k] == 1) {
             zv[k] = fmax(lv[k], xk + dk);
-            if (zv[k] == lv[k]) red[0] += 1.0;
+            if (zv[k] == lv[k]) red[SUBSM_IWORD] += 1.0;
           } else if (nbk[k] == 2) {
             const double t1 = fmax(lv[k], xk + dk);
             zv[k] = fmin(uv[k], t1);
-            if (zv[k] == lv[k] || zv[k] == uv[k]) red[0] += 1.0;
+            if (zv[k] == lv[k] || zv[k] == uv[k]) red[SUBSM_IWORD] += 1.0;
           } else if (nbk[k] == 3) {
             zv[k] = fmin(uv[k], xk + dk);
-            if (zv[k] == uv[k]) red[0] += 1.0;
+            if (zv[k] == uv[k]) red[SUBSM_IWORD] += 1.0;
           }
         } else {
           zv[k] = xk + dk;
@@ -300,16 +300,16 @@ __global__ __launch_bounds__(BLOCK) void wide_r_pass_kernel(int64_t n, const T *
         zv[k] = (double)(T)zv[k];
       }
       dv[k] = zv[k] - xv[k];              // mainlb :720-722 (lnsrlb_begin_kernel)
-      red[1] = red[1] + dv[k] * gv[k];    // dd_p (:2824-2827) == g'd (:2244)
-      red[2] = red[2] + dv[k] * dv[k];    // dtd (:2196)
+      red[SUBSM_DDP] = red[SUBSM_DDP] + dv[k] * gv[k];    // dd_p (:2824-2827) == g'd (:2244)
+      red[SUBSM_DTD] = red[SUBSM_DTD] + dv[k] * dv[k];    // dtd (:2196)
       if (wt.do_stpmx && nbk[k] != 0) {   // :2206-2225
         const double a1 = dv[k];
         if (a1 < 0.0 && nbk[k] <= 2) {
           const double a2 = lv[k] - xv[k];
-          red[3] = fmin(red[3], a2 >= 0.0 ? 0.0 : a2 / a1);
+          red[SUBSM_STPMX] = fmin(red[SUBSM_STPMX], a2 >= 0.0 ? 0.0 : a2 / a1);
         } else if (a1 > 0.0 && nbk[k] >= 2) {
           const double a2 = uv[k] - xv[k];
-          red[3] = fmin(red[3], a2 <= 0.0 ? 0.0 : a2 / a1);
+          red[SUBSM_STPMX] = fmin(red[SUBSM_STPMX], a2 <= 0.0 ? 0.0 : a2 / a1);
         }
       }
     }
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(BLOCK) void wide_r_pass_kernel(int64_t n, const T *
     if (wt.rout) st<W>(wt.rout + i, gv);  // r = g (:2236)
     if (wt.xout) st<W>(wt.xout + i, zv);  // the first trial point x = z (:2265); may alias wt.x and pd (rows read above)
   });
-  block_reduce_store<4>(red, 3, 1, 0, part, MAX_BLOCKS);
+  block_reduce_store<SUBSM_SIZE>(red, SUBSM_NSUM, 1, 0, part, MAX_BLOCKS);
 }
 template <typename T>
 void launch_wide_r_pass(Queue &q, int64_t n, WStore<T> w, int head, int col, const CoefWide &cf, const iw_t *iwhere,
@@ -333,7 +333,7 @@ void launch_wide_r_pass(Queue &q, int64_t n, WStore<T> w, int head, int col, con
     hipLaunchKernelGGL((wide_r_pass_kernel<T, false>), dim3(gr), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld,
                        w.m, head, col, cf, iwhere, nbd8, ub, wt, pe, pr, pd, w.wy + slot, w.ws + slot, q.part());
   LB_LAUNCHED(q);
-  launch_finalize(q, gr, 3, 1, 0);
+  launch_finalize(q, gr, SUBSM_NSUM, 1, 0);
 }
 
 // out_i = src_i on the rows selected (want_free: iwhere <= 0, else iwhere > 0), 0 elsewhere

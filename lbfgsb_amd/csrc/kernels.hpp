@@ -7,18 +7,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "res_layout.hpp"  // the slot layouts of the results, MAXM, maxc_for, RES_MAX, the split pass's sizes
 
 namespace lbk {
 
 constexpr int BLOCK = 256;        // 4 wave64 per workgroup
 constexpr int MAX_BLOCKS = 2048;  // 256 CUs x 8 workgroups, grid-stride beyond that
 constexpr int GRAM_BLOCKS = 1024;
-constexpr int MAXM = 32;          // LBFGSB_MAX_M
-constexpr int RES_MAX = 8 * MAXM + 16;  // >= 6*MC slots of cmprlb_wtv(newrow), 8*MC+15 of update_scan(newrow)
-// update pass with formk's new-row sums at col - 1 > 20 (k_update.hip): several launches over a part of the columns
-// each; their results land behind the merged layout in d_res (split_base) and are merged into the one-launch layout
-// (any col - 1 > 20, k_update.hip "the split pass": parts of <= 16 columns)
-constexpr int SPLIT_SLOTS = 8 * 20 + 16, SPLIT_COLS = 16, SPLIT_MAXPARTS = 64;
 
 // per-context launch options (lbfgsb_hip_set_option; nothing is read from the environment)
 struct Tune {
@@ -125,9 +120,6 @@ struct Pend {
 int grid_for(int64_t n, int vec);
 // the same for the passes over W: as many workgroups as are resident for `kernel` (1-3 per CU)
 int grid_for_w(const Queue &q, int64_t n, int vec, const void *kernel = nullptr);
-// compile-time column capacity the kernels are unrolled to for `col` pairs (5, 10, 20, 32).
-// Reduction slots that depend on col use MC = maxc_for(col) as their stride.
-int maxc_for(int col);
 
 // ---- one-off (START) ----------------------------------------------------
 // active (ref :965-1040): clip x, init iwhere.  res: [0]=#projected (sum),
@@ -155,7 +147,7 @@ template <typename T>
 void launch_dot(Queue &q, int64_t n, const T *a, const T *b);
 
 // ---- W'v (the WS/WY correction-pair matvec) -------------------------------
-// res sum-slots [0..col) = Wy' v, [MC..MC+col) = Ws' v (logical column order)
+// res: WtvSlots{maxc_for(col)} (logical column order)
 template <typename T>
 void launch_wtv(Queue &q, int64_t n, WStore<T> w, int head, int col, const T *v);
 template <typename T>
@@ -163,9 +155,7 @@ void launch_wtv_nofinalize(Queue &q, int64_t n, WStore<T> w, int head, int col, 
 
 // ---- cauchy (ref :1157-1532) ----------------------------------------------
 // scan (:1270-1330): updates iwhere, writes tbrk (breakpoint t_i > 0; +inf = moves
-// without bound; -1 = does not move).  With MC = (col ? maxc_for(col) : 0), res sum-slots:
-// [0..col) Wy'd, [MC..MC+col) Ws'd, [2MC] f1, [2MC+1] nbreak, [2MC+2] #moving-without-
-// breakpoint, [2MC+3] #of those with g!=0; min-slot [2MC+4] = bkmin (+inf if none)
+// without bound; -1 = does not move).  res: CauchyScanSlots::of(col)
 template <typename T>
 void launch_cauchy_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
                         const int32_t *nbd, const T *g, iw_t *iwhere, T *tbrk,
@@ -301,10 +291,8 @@ void launch_formk_gram(Queue &q, int64_t n, WStore<T> w, int head, int col,
                        const iw_t *iwhere);
 
 // cmprlb + the first matvec of subsm (W'r, :2742-2754) in one pass over W.
-// res sum-slots (MC = maxc_for(col)): [0..col) Wy'r, [MC..MC+col) Ws'r; with newrow also the
-// new row/column of formk's WN1 for the pair in logical column col-1 (ref :1756-1793):
-// [2MC..) sum_free Wy_new Wy_j, [3MC..) sum_act Ws_new Ws_j, [4MC..) sum_act Ws_new Wy_j,
-// [5MC..) sum_free Ws_j Wy_new.  r itself is not stored: launch_subsm_update recomputes it.
+// res: CmprlbWtvSlots{maxc_for(col), newrow} -- W'r; with newrow also the new row/column of formk's WN1 for the
+// pair in logical column col-1 (ref :1756-1793).  r itself is not stored: launch_subsm_update recomputes it.
 // The Cauchy point is evaluated per row from (x, g, iwhere, tsum), see xcp_free in kernels_common.hpp.
 template <typename T>
 void launch_cmprlb_wtv(Queue &q, int64_t n, const T *x, const T *g, double tsum,
@@ -330,8 +318,8 @@ int small_sort_cap();
 // cf = the coefficients the preceding launch_cmprlb_wtv used (all zero, with tsum = 0, for the
 // reference's unconstrained shortcut r = -g, cmprlb :1560-1563: the general formula then gives
 // exactly -g); wv = K^-1 W'r.
-// res sum-slots: [0] = #bound hits (iword), [1] = dd_p (= g'(z-x)), [2] = dtd ; min-slot [3] =
-// stpmx candidate.  xout (= the caller's x, or nullptr): also store the first trial point of the
+// res (SubsmSlot): sums #bound hits (iword), dd_p (= g'(z-x)), dtd ; min = stpmx candidate.
+// xout (= the caller's x, or nullptr): also store the first trial point of the
 // line search, x = z, when its step length is known to be 1 (:2265).  pr: the vector a pending
 // pair's y is formed from (r of the previous line search); rout / tvec: where r = g and t = x are
 // stored -- nullptr with ping-pong iterate buffers, where they are a change of roles, not copies.
@@ -375,17 +363,13 @@ void launch_lnsrlb_eval(Queue &q, int64_t n, const T *x, const T *l, const T *u,
                         const int32_t *nbd, const T *g, const T *d);
 
 // ---- mainlb :812-824 + matupd (ref :2291-2346) --------------------------------
-// y = g - r, s = stp*d stored into column itail (1-based physical); with
-// MC = maxc_for(col-1), res sum: [0..col-1) = s'Wy_j, [MC..MC+col-1) = Ws_j's for the
-// col-1 older columns (logical order from head), [2MC] = y'y
+// y = g - r, s = stp*d stored into column itail (1-based physical);
+// res: UpdatePairsSlots{maxc_for(col-1)} over the col-1 older columns (logical order from head)
 template <typename T>
 void launch_update_pairs(Queue &q, int64_t n, const T *g, const T *r, const T *d, double stp,
                          WStore<T> w, int head, int col, int itail);
 
-// the two above fused (one pass over the old columns); slots, MC = maxc_for(col-1):
-// [0,MC) s'Wy_j | [MC,2MC) Ws_j's | [2MC] y'y | [2MC+1,3MC+1) Wy_j'd | [3MC+1] y'd |
-// [3MC+2,4MC+2) Ws_j'd | [4MC+2] s'd | [4MC+3] f1, nbreak, nunb, nunbnz | [4MC+7] g'd |
-// [4MC+8] #iwhere changes | min [4MC+9] bkmin | max [4MC+10] |proj g|
+// the two above fused (one pass over the old columns); res: UpdScanSlots{maxc_stride(col-1), newrow}
 template <typename T>
 void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
                         const nb_t *nbd, const T *g, const T *r, const T *d, int dimpl,
@@ -401,10 +385,6 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
 // <= 8 values each and the nbd byte stream carries nbd | l-index << 2 | u-index << 5 (kernels_common.hpp).
 // cand_hi >= 0: rows whose breakpoint t lies in [0, cand_hi] are appended (unordered) to
 // ckeys / cidx (capacity ccap), *ccount = how many there are (zeroed by the launch)
-// newrow (col - 1 <= 10): 4 MC + 4 more sum slots in front of the min / max slots -- the new
-// row/column of formk's WN1 with the PRE-walk free set (layout: update_scan_kernel in
-// k_update.hip); min slot = 4 MC + 9 + (newrow ? 4 MC + 4 : 0), max slot behind it
-inline int update_scan_extra(int nold, int newrow);
 // Ws/Wy slot of logical column col-1 <- the pending pair (paths without a subspace pass)
 void launch_nbd_pack(Queue &q, int64_t n, const int32_t *nbd, nb_t *out);
 // Dictionary-coded bounds (ub bit 3 = UB_DICT, kernels_common.hpp): bound arrays with <= 8 distinct values each.
@@ -465,7 +445,7 @@ void launch_tile_axpy(Queue &q, int64_t n, WStore<T> w, int head, int tc, const 
 // (xcp_row), neither xcp nor r0 exists as a vector.  last: the finished sum is the Newton direction; the projected
 // step (:2780-2816), dd_p (:2824-2827), d = z - x, dtd, the stpmx ratios (:2196-2225) and the stores of
 // subsm_update_kernel (trial x / z, d, t, r: any of them may be nullptr) follow in the same kernel.
-// res (last only): sum [0] = #bound hits, [1] = dd_p = g'd, [2] = dtd ; min [3] = stpmx
+// res (last only): SubsmSlot
 template <typename T>
 struct WideTail {
   const T *x, *g, *l, *u;
@@ -516,18 +496,6 @@ template <typename T>
 void launch_halo_pack(Queue &q, int64_t n, const T *x, double *out);
 // res sum [0] = *d_val (this rank's part of an objective value the caller computed on the device)
 void launch_scalar_partial(Queue &q, const double *d_val);
-
-// the stride of the update pass's result layout: the column capacity of the kernel that ran, or -- beyond 32
-// columns, where the pass is split into sub-launches and merged -- the next multiple of 32
-inline int maxc_stride(int col) { return col <= MAXM ? maxc_for(col) : (col + 31) / 32 * 32; }
-inline int update_scan_extra(int nold, int newrow) { return newrow ? 4 * maxc_stride(nold) + 4 : 0; }
-// where the sub-launches of a split update pass put their results in d_res: behind the merged layout at `dst`
-inline int split_base(int nold, int dst) { return std::max(RES_MAX + 16, dst + 8 * maxc_stride(nold) + 32); }
-inline int split_parts(int nold, int cols = SPLIT_COLS) { return (nold + cols - 1) / cols; }
-// d_res doubles a context with m pairs needs for a split update pass (parts of >= 5 columns)
-inline size_t split_res_len(int m) {
-  return m <= 5 ? 0 : (size_t)split_base(m, 1) + (size_t)split_parts(m, 5) * SPLIT_SLOTS + 8;
-}
 
 // finalize: partials -> d_res (nsum sums, then nmin mins, then nmax maxes); takes parked jobs along
 void launch_finalize(Queue &q, int nblocks, int nsum, int nmin, int nmax);

@@ -3,8 +3,8 @@
 // Mirrors the reverse-communication state machine of the reference `mainlb`
 // (src/lbfgsb.f90:312-949): same task protocol, same isave/dsave/lsave slots,
 // same failure/refresh branches.  Every n-dimensional operation is a kernel
-// launch from the k_*.hip files; every 2m x 2m operation is host code from
-// host_dense.hpp.  One host thread per context, one HIP stream per context.
+// launch from the k_*.hip files (which of a pass's results is what: res_layout.hpp, shared
+// with the kernels); every 2m x 2m operation is host code from host_dense.hpp.  One host thread per context, one HIP stream per context.
 //
 // One steady-state iteration on a bounded problem with col <= 32 pairs stored (DESIGN.md 4a
 // has the why) -- two passes over W (beyond 21 pairs the first one is two launches over half of
@@ -264,8 +264,9 @@ class Solver final : public lbfgsb_hip_ctx {
     // reduction scratch
     const size_t E = (size_t)2 * m * m + m;
     if (m > lbk::MAXM) {
-      DEFER_OFF = 8 * lbk::maxc_stride(m - 1) + 24, SPEC_OFF = DEFER_OFF + 8;
-      q.split_base_min = DEFER_OFF + 8;  // (<= split_base(m, 1), which split_res_len sizes d_res for)
+      const int merged = lbk::UpdScanSlots{lbk::maxc_stride(m - 1), true}.size();  // the longest merged layout
+      DEFER_OFF = merged + lbk::DEFER_PAD, SPEC_OFF = DEFER_OFF + 8;
+      q.split_base_min = merged + lbk::SPLIT_PAD;  // (<= split_base(m, 1), which split_res_len sizes d_res for)
     }
     // (the widest phase or a from-scratch Gram; behind DEFER_OFF the four deferred sums, behind SPEC_OFF the
     //  speculative freev counts + formk patch of a trial point: 4 + E + 1)
@@ -385,8 +386,8 @@ class Solver final : public lbfgsb_hip_ctx {
   // DEFER_OFF: four more slots (3 sums + 1 minimum) behind the widest phase -- the line-search sums of a
   // storing pass that did not wait for them (LBFGSB_F_DEFER_LNSRCH); while defer_live they travel with
   // every fetch and are reduced like the rest.
-  // (m > 32: the merged layout of the split update pass is 8 maxc_stride(m - 1) + 15 doubles long, its parts start 32
-  //  doubles behind it (split_base): the deferred sums sit in between)
+  // (m > 32: behind the merged layout of the split update pass, in front of its parts: DEFER_PAD, SPLIT_PAD in
+  //  res_layout.hpp)
   int DEFER_OFF = lbk::RES_MAX;
   // SPEC_OFF: the sums of a SPECULATIVE freev + formk-patch chain queued behind the evaluation of a trial point
   // (phase_entry): spec_live_len slots, all sums, fetched and reduced with that evaluation's fetch
@@ -959,8 +960,7 @@ class Solver final : public lbfgsb_hip_ctx {
         } else {
           c2 = col, it2 = itail % m + 1, h2 = head % m + 1;
         }
-        const int MCo = lbk::maxc_stride(c2 - 1);
-        const int NX = lbk::update_scan_extra(c2 - 1, nr_flag(c2));
+        const lbk::UpdScanSlots S{lbk::maxc_stride(c2 - 1), nr_flag(c2) != 0};
         clk_begin(1);
         q.res_off = fo;
         // (the MC = 20 instantiation with the new-row sums has no registers for the hand-over)
@@ -1003,7 +1003,7 @@ class Solver final : public lbfgsb_hip_ctx {
           spec_live_len = 4 + 2 * sf_upcl * sf_upcl + sf_upcl + 1;
           sfv.parity = par & 1, sfv.upcl = sf_upcl, sfv.head = h2, sfv.col = c2, sfv.iter = iter + 1, sfv.x = x;
         }
-        CHK(fetch(fo + 4 * MCo + 9 + NX, 1, 1));
+        CHK(fetch(fo + S.nsum(), 1, 1));
         if (do_sfv) {
           const int nl = spec_live_len;
           spec_live_len = 0;
@@ -1018,11 +1018,11 @@ class Solver final : public lbfgsb_hip_ctx {
         if (chi >= 0.0) CHK(spec_land(c2, chi));
         if (fo) *f = f_scale * h_res[0];
         const double *R = h_res + fo;
-        if (store_iw) iw_dirty += R[4 * MCo + 8];  // (the pass stored the entries that changed)
-        L.spec_iw_changed = store_iw ? R[4 * MCo + 8] : 0.0;
-        gd = R[4 * MCo + 7];
-        spec_sbgnrm = R[4 * MCo + 10 + NX];
-        std::memcpy(spec.res.data(), R, sizeof(double) * (4 * MCo + 11 + NX));
+        if (store_iw) iw_dirty += R[S.iw_changed()];  // (the pass stored the entries that changed)
+        L.spec_iw_changed = store_iw ? R[S.iw_changed()] : 0.0;
+        gd = R[S.gd()];
+        spec_sbgnrm = R[S.pgnorm()];
+        std::memcpy(spec.res.data(), R, sizeof(double) * S.size());
         spec.valid = true;  // dropped below unless dcsrch accepts this point
         spec.x = x, spec.g = g, spec.stp = stp_here, spec.head = h2, spec.col = c2, spec.itail = it2;
         tbrk_valid = false;
@@ -1288,7 +1288,7 @@ class Solver final : public lbfgsb_hip_ctx {
                                     newrow ? 1 : 0, r, d, pend);
           clk_end(0);
           q.res_off = 0;
-          npre = (newrow ? 6 : 2) * lbk::maxc_for(col);
+          npre = lbk::CmprlbWtvSlots{lbk::maxc_for(col), newrow}.size();
         }
       }
       CHK(fetch(4 + npre + neager, 0, 0));
@@ -1635,27 +1635,19 @@ class Solver final : public lbfgsb_hip_ctx {
     const int c2 = spec.col, nold = c2 - 1;
     const bool full = c2 == col;  // (the pass ran with head + 1)
     if (!(full ? (col == m && spec.head == head % m + 1) : (c2 == col + 1 && spec.head == head))) return 0;
-    const int MCo = lbk::maxc_stride(nold);
-    const int NX = lbk::update_scan_extra(nold, nr_flag(c2));
+    const lbk::UpdScanSlots S{lbk::maxc_stride(nold), nr_flag(c2) != 0};
     const double *R = spec.res.data();
-    const int shift = full ? 1 : 0;
     if (full) {
-      const int MC1 = lbk::maxc_for(1);
+      const auto S1 = lbk::CauchyScanSlots::of(1);
       lbk::launch_cauchy_scan<T>(q, n, x, l, u, nbd, g, iwhere, tbrk, W(), head, 1);
-      CHK(fetch(2 * MC1 + 4, 1, 0));
-      scan.p[0] = h_res[0], scan.p[col] = h_res[MC1];
+      CHK(fetch(S1.nsum(), 1, 0));
+      scan.take(h_res, S1, col, 1);
       tbrk_valid = true;
       if (flags & LBFGSB_F_MIRROR_INDEX) iw_dirty += 1.0;  // (the evaluation held its iwhere stores back)
-    } else if ((flags & LBFGSB_F_MIRROR_INDEX) && R[4 * MCo + 8] > 0.0) {
+    } else if ((flags & LBFGSB_F_MIRROR_INDEX) && R[S.iw_changed()] > 0.0) {
       lbk::launch_iwhere_update<T>(q, n, x, l, u, nbd, g, iwhere), iw_dirty += 1.0;
     }
-    for (int j = shift; j < col; ++j) {
-      scan.p[j] = R[2 * MCo + 1 + j - shift];
-      scan.p[col + j] = R[3 * MCo + 2 + j - shift];
-    }
-    scan.f1 = R[4 * MCo + 3], scan.nbreak = R[4 * MCo + 4];
-    scan.nunb = R[4 * MCo + 5], scan.nunbnz = R[4 * MCo + 6];
-    scan.bkmin = R[4 * MCo + 9 + NX];
+    scan.take(R, S, col, nold, full ? 1 : 0);  // (memory full: the pass's columns are one further up now)
     scan.ready = true;
     nskip_reused++;
     return 0;
@@ -1698,25 +1690,26 @@ class Solver final : public lbfgsb_hip_ctx {
       itail = itail % m + 1;
       head = head % m + 1;
     }
-    const int MCo = lbk::maxc_stride(col - 1);
     double rr;
+    const double *sy_row, *ss_col;  // Sy's new row, Ss's new column
     std::vector<double> wsy, wss;  // (m > 32: Sy's new row, Ss's new column from the tile passes)
     const bool unfused = wide() && !wide_fused();
     if (unfused) {
       CHK(ensure_d(x));
       CHK(wide_matupd(g, stp, head, col, wsy, wss, rr));
       spec.valid = false, pend.on = 0, scan.ready = false;
+      sy_row = wsy.data(), ss_col = wss.data();
     } else if (cnstnd || two_pass) {
       // the next loop trip starts with cauchy: do its n-loop in the same pass over W --
       // unless that pass already ran as the evaluation of the accepted trial point
       const bool reuse = spec.valid && spec.x == x && spec.g == g && spec.stp == stp &&
                          spec.head == head && spec.col == col && spec.itail == itail;
-      const int NX = lbk::update_scan_extra(col - 1, nr_flag(col));
+      const lbk::UpdScanSlots S{lbk::maxc_stride(col - 1), nr_flag(col) != 0};
       if (debug_walk) std::fprintf(stderr, "[update] iter %d stp %g reuse %d\n", iter, stp, (int)reuse);
       if (!reuse) sfv.valid = false;
       if (reuse) {
-        std::memcpy(h_res, spec.res.data(), sizeof(double) * (4 * MCo + 11 + NX));
-        if ((flags & LBFGSB_F_MIRROR_INDEX) && h_res[4 * MCo + 8] > 0.0)
+        std::memcpy(h_res, spec.res.data(), sizeof(double) * S.size());
+        if ((flags & LBFGSB_F_MIRROR_INDEX) && h_res[S.iw_changed()] > 0.0)
           lbk::launch_iwhere_update<T>(q, n, x, l, u, nbd, g, iwhere), iw_dirty += 1.0;  // the pass held it back
       } else {
         clk_begin(1);
@@ -1727,43 +1720,34 @@ class Solver final : public lbfgsb_hip_ctx {
         clk_end(1);
         spcand.valid = false;
         if (chi >= 0.0) CHK(spec_queue(x, l, u, g, head, col, stp));
-        CHK(fetch(4 * MCo + 9 + NX, 1, 1));
+        CHK(fetch(S.nsum(), 1, 1));
         if (chi >= 0.0) CHK(spec_land(col, chi));
-        iw_dirty += h_res[4 * MCo + 8];
+        iw_dirty += h_res[S.iw_changed()];
       }
       nrpre.valid = false;
-      if (NX) {  // formk's new row/column with the pre-walk free set (update_scan_kernel NEWROW)
-        const int X0 = 4 * MCo + 9, nold_ = col - 1;
+      if (S.newrow) {  // formk's new row/column with the pre-walk free set (update_scan_kernel NEWROW)
         for (int k = 0; k < 4; ++k) {
-          for (int j = 0; j < nold_; ++j) nrpre.t[k][j] = h_res[X0 + k * MCo + j];
-          nrpre.t[k][nold_] = h_res[X0 + 4 * MCo + k];
+          for (int j = 0; j < col - 1; ++j) nrpre.t[k][j] = h_res[S.nr_vec(k, j)];
+          nrpre.t[k][col - 1] = h_res[S.nr_scalar(k)];
         }
         nrpre.valid = true, nrpre.col = col;
       }
       spec.valid = false;
       tbrk_valid = false;
       pend.on = 1, pend.stp = stp, pend.impl = d_impl ? 1 : 0;  // committed by this call's subspace pass
-      rr = h_res[2 * MCo];
-      const int nold = col - 1;
-      for (int j = 0; j < nold; ++j) {
-        scan.p[j] = h_res[2 * MCo + 1 + j];
-        scan.p[col + j] = h_res[3 * MCo + 2 + j];
-      }
-      scan.p[col - 1] = h_res[3 * MCo + 1];
-      scan.p[2 * col - 1] = h_res[4 * MCo + 2];
-      scan.f1 = h_res[4 * MCo + 3], scan.nbreak = h_res[4 * MCo + 4];
-      scan.nunb = h_res[4 * MCo + 5], scan.nunbnz = h_res[4 * MCo + 6];
-      scan.bkmin = h_res[4 * MCo + 9 + NX];
+      rr = h_res[S.yy()], sy_row = h_res + S.sy(0), ss_col = h_res + S.ss(0);
+      scan.take(h_res, S, col, col - 1);
+      scan.p[col - 1] = h_res[S.yd()], scan.p[2 * col - 1] = h_res[S.sd()];  // the new pair's column
       scan.ready = true;
     } else {
       CHK(ensure_d(x));
       lbk::launch_update_pairs<T>(q, n, g, r, d, stp, W(), head, col, itail);
-      CHK(fetch(2 * MCo + 1, 0, 0));
-      rr = h_res[2 * MCo];
+      const lbk::UpdatePairsSlots P{lbk::maxc_for(col - 1)};
+      CHK(fetch(P.size(), 0, 0));
+      rr = h_res[P.yy()], sy_row = h_res + P.sy(0), ss_col = h_res + P.ss(0);
     }
     theta = rr / dr;
-    matupd_small(col, iupdat, unfused ? wsy.data() : h_res, unfused ? wss.data() : h_res + MCo,
-                 stp == 1.0 ? dtd : stp * stp * dtd, dr);
+    matupd_small(col, iupdat, sy_row, ss_col, stp == 1.0 ? dtd : stp * stp * dtd, dr);
     info = lbh::formt(m, wt.data(), sy.data(), ss.data(), col, theta);  // :849
     if (info != 0) {
       if (ipr >= 1)

@@ -134,7 +134,8 @@
     const void *x = nullptr, *g = nullptr;
     double stp = 0.0;
     int head = 0, col = 0, itail = 0;
-    std::vector<double> res = std::vector<double>(8 * (size_t)LBFGSB_MAX_M + 64, 0.0);  // (the widest merged layout)
+    std::vector<double> res =
+        std::vector<double>(lbk::UpdScanSlots{lbk::maxc_stride(LBFGSB_MAX_M - 1), true}.size(), 0.0);  // (the widest)
   } spec;
   int commit_pending(const T *g, int col, int head) {
     if (pend.on) {

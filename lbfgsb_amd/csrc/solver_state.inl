@@ -165,12 +165,9 @@
       return 0;
     }
     lbk::launch_wtv<T>(q, n, W(), head, col, (const T *)v);
-    const int MC = lbk::maxc_for(col);
-    CHK(fetch(2 * MC, 0, 0));
-    for (int j = 0; j < col; ++j) {
-      out[j] = h_res[j];
-      out[col + j] = h_res[MC + j];
-    }
+    const lbk::WtvSlots S{lbk::maxc_for(col)};
+    CHK(fetch(S.size(), 0, 0));
+    S.decode(h_res, col, out);
     return 0;
   }
   int k_launch(int which, const void *x, const void *g, int col, int head) override {

@@ -227,6 +227,7 @@
     // together with freev's counts (one fetch for both) and its sums are in pre[].
     const int MC = lbk::maxc_for(col);
     const bool newrow = do_formk && updatd;
+    const lbk::CmprlbWtvSlots S{MC, newrow};
     const double *res = pre;
     const int ipr = quiet ? -1 : print_level;
     if (closed) {
@@ -251,16 +252,13 @@
       lbk::launch_cmprlb_wtv<T>(q, n, x, g, gcp.tsum, iwhere, W(), head, col, theta, cf,
                                 newrow ? 1 : 0, r, d, pend);
       clk_end(0);
-      CHK(fetch((newrow ? 6 : 2) * MC, 0, 0));
+      CHK(fetch(S.size(), 0, 0));
       res = h_res;
     }
     double *wv = &wa8m[0];
     if (!closed) {
       nthreepass++;
-      for (int i = 0; i < col; ++i) {
-        wv[i] = res[i];
-        wv[col + i] = theta * res[MC + i];
-      }
+      S.wtv().decode(res, col, wv, theta);
     }
     if (do_formk) {
       double nr[4 * lbk::MAXM];
@@ -274,7 +272,8 @@
           }
         }
       } else if (newrow) {
-        std::memcpy(nr, res + 2 * MC, sizeof(double) * 4 * MC);
+        for (int k = 0; k < 4; ++k)
+          for (int j = 0; j < col; ++j) nr[k * MC + j] = res[S.nr(k, j)];
       }
       CHK(formk_incremental(col, head, updatd, iupdat, nr, MC));
       formk_factor(col, theta, info);
@@ -288,11 +287,8 @@
       clk_begin(0);
       lbk::launch_cmprlb_wtv<T>(q, n, x, g, gcp.tsum, iwhere, W(), head, col, theta, cm_cf, 0, r, d, pend);
       clk_end(0);
-      CHK(fetch(2 * MC, 0, 0));
-      for (int i = 0; i < col; ++i) {
-        wv[i] = h_res[i];
-        wv[col + i] = theta * h_res[MC + i];
-      }
+      CHK(fetch(S.wtv().size(), 0, 0));
+      S.wtv().decode(h_res, col, wv, theta);
       closed = false;
       nclosed--, nthreepass++;
     }
@@ -348,10 +344,18 @@
       ndeferred++;
       return 0;
     }
-    CHK(fetch(3, 1, 0));
+    CHK(fetch(lbk::SUBSM_NSUM, 1, 0));
     return subspace_land(x, l, u, nbd, g, h_res, iword, info);
   }
 
+  // the line-search set-up values from the four results of a storing pass (SubsmSlot); true: the projected step is
+  // taken as it is (:2820, :2828), false: the backtracking branch follows
+  bool ls_from_subsm(const double *R, int &iword) {
+    iword = R[lbk::SUBSM_IWORD] > 0.0 ? 1 : 0;
+    ls.ready = true, ls.x_is_z = ls_unit_step;
+    ls.gd = R[lbk::SUBSM_DDP], ls.dtd = R[lbk::SUBSM_DTD], ls.stpmx = R[lbk::SUBSM_STPMX];
+    return iword == 0 || ls.gd <= 0.0;
+  }
   // what follows the storing pass's sums (in the same call, or -- deferred -- in the next one): the
   // line-search set-up values, and the backtracking branch (:2830-2879) when the projected step points uphill
   lbk::Coef sub_cw;
@@ -363,16 +367,9 @@
     const double theta = sub_theta;
     const int col = sub_col, head = sub_head;
     const lbk::Coef &cw = sub_cw;
-    if (R[0] >= 1.0e29)  // (k_subsm.hip: a free row outside its tile's front run -- the layout was not re-sorted)
+    if (R[lbk::SUBSM_IWORD] >= 1.0e29)  // (k_subsm.hip: a free row outside its tile's front run -- the layout was not re-sorted)
       return fail(LBFGSB_E_STATE, "storing pass: the tile-local layout of W is older than the free set");
-    iword = R[0] > 0.0 ? 1 : 0;
-    const double dd_p = R[1];
-    ls.ready = true;
-    ls.x_is_z = ls_unit_step;
-    ls.gd = dd_p;
-    ls.dtd = R[2];
-    ls.stpmx = R[3];
-    if (iword == 0 || dd_p <= 0.0) {  // :2820, :2828
+    if (ls_from_subsm(R, iword)) {
       if (ipr >= 99) std::fprintf(rep.out, "\n----------------exit SUBSM --------------------\n\n");  // :2883
       return 0;
     }

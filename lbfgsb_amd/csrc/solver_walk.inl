@@ -69,6 +69,13 @@
     bool ready = false;
     std::vector<double> p;  // 2 m
     double f1 = 0, nbreak = 0, nunb = 0, nunbnz = 0, bkmin = 0;
+    // from the results R of a pass that ran cauchy's n-loop (layout S: CauchyScanSlots or UpdScanSlots): the
+    // products of its first ncols columns, `shift` columns up in the col-wide halves of p, and the scalars
+    template <typename S>
+    void take(const double *R, S s, int col, int ncols, int shift = 0) {
+      for (int j = 0; j < ncols; ++j) p[shift + j] = R[s.p_wy(j)], p[col + shift + j] = R[s.p_ws(j)];
+      f1 = R[s.f1()], nbreak = R[s.nbreak()], nunb = R[s.nunb()], nunbnz = R[s.nunbnz()], bkmin = R[s.bkmin()];
+    }
   } scan;
 
   // The long stretch of a first-iteration walk (col = 0, records of 4 doubles: t, row, d, z, in order): the
@@ -159,7 +166,6 @@
       return 0;
     }
     const int col2 = 2 * col;
-    const int MC = col ? lbk::maxc_for(col) : 0;
     if (ipr >= 99) std::fprintf(rep.out, "\n---------------- CAUCHY entered-------------------\n");
     auto leave = [&](double tsum_, double lt, int64_t li) -> int {  // update() :1519-1530
       CHK(close_gcp(tsum_, lt, li));
@@ -174,13 +180,9 @@
       lbk::launch_cauchy_scan<T>(q, n, x, l, u, nbd, g, iwhere, tbrk, W(), head, col);
       iw_dirty += 1.0;  // (this scan does not count the entries it changes)
       tbrk_valid = true;
-      CHK(fetch(2 * MC + 4, 1, 0));
-      for (int j = 0; j < col; ++j) {
-        scan.p[j] = h_res[j];
-        scan.p[col + j] = h_res[MC + j];
-      }
-      scan.f1 = h_res[2 * MC], scan.nbreak = h_res[2 * MC + 1], scan.nunb = h_res[2 * MC + 2];
-      scan.nunbnz = h_res[2 * MC + 3], scan.bkmin = h_res[2 * MC + 4];
+      const auto S = lbk::CauchyScanSlots::of(col);
+      CHK(fetch(S.nsum(), 1, 0));
+      scan.take(h_res, S, col, col);
     }
     scan.ready = false;
     for (int j = 0; j < col2; ++j) p[j] = scan.p[j];

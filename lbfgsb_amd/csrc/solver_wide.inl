@@ -16,9 +16,9 @@ int wide_wtv(const T *v, int col, int head, double *outY, double *outS) {
     const int tc = std::min(lbk::MAXM, col - j0);
     const int h = (head - 1 + j0) % m + 1;
     lbk::launch_wtv<T>(q, n, W(), h, tc, v);
-    const int MC = lbk::maxc_for(tc);
-    CHK(fetch(2 * MC, 0, 0));
-    for (int j = 0; j < tc; ++j) outY[j0 + j] = h_res[j], outS[j0 + j] = h_res[MC + j];
+    const lbk::WtvSlots S{lbk::maxc_for(tc)};
+    CHK(fetch(S.size(), 0, 0));
+    for (int j = 0; j < tc; ++j) outY[j0 + j] = h_res[S.wy(j)], outS[j0 + j] = h_res[S.ws(j)];
   }
   return 0;
 }
@@ -55,9 +55,9 @@ int wide_cauchy_scan(const T *x, const T *l, const T *u, const int32_t *nbd, con
   lbk::launch_cauchy_scan<T>(q, n, x, l, u, nbd, g, iwhere, tbrk, W(), head, 0);
   iw_dirty += 1.0;
   tbrk_valid = true;
-  CHK(fetch(4, 1, 0));
-  scan.f1 = h_res[0], scan.nbreak = h_res[1], scan.nunb = h_res[2], scan.nunbnz = h_res[3];
-  scan.bkmin = h_res[4];
+  const auto S = lbk::CauchyScanSlots::of(0);
+  CHK(fetch(S.nsum(), 1, 0));
+  scan.take(h_res, S, col, 0);
   if (col > 0) {
     lbk::launch_cauchy_dvec<T>(q, n, g, tbrk, xp);
     CHK(wide_wtv(xp, col, head, &scan.p[0], &scan.p[col]));
@@ -255,10 +255,7 @@ int wide_unfused_r(const T *x, const T *l, const T *u, const int32_t *nbd, const
 }
 int wide_land(const T *x, const T *l, const T *u, const int32_t *nbd, const T *g, const double *R, int &iword) {
   wl.pending = false;
-  iword = R[0] > 0.0 ? 1 : 0;
-  const double dd_p = R[1];
-  ls.ready = true, ls.x_is_z = ls_unit_step, ls.gd = dd_p, ls.dtd = R[2], ls.stpmx = R[3];
-  if (iword == 0 || dd_p <= 0.0) return 0;  // :2820, :2828
+  if (ls_from_subsm(R, iword)) return 0;
   // the backtracking branch (:2830-2879): from the iterate again, through the unfused steps
   ls.ready = false, d_impl = z_in_x = false, z_valid = false;
   if (ls.x_is_z && !pp) HIPCHK(hipMemcpyAsync(xmut, t, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, stream));
@@ -346,7 +343,7 @@ int wide_subspace(const T *x, const T *l, const T *u, const int32_t *nbd, const 
         ndeferred++;
         return 0;
       }
-      CHK(fetch(3, 1, 0));
+      CHK(fetch(lbk::SUBSM_NSUM, 1, 0));
       return wide_land(x, l, u, nbd, g, h_res, iword);
     }
     CHK(commit_pending(g, col, head));  // (the unfused steps read the newest pair from W)

@@ -180,7 +180,6 @@ inline double pend_sx_h(double t, double x, Pend pe) {
 }
 }  // namespace
 
-int maxc_for(int col) { return col <= 5 ? 5 : col <= 10 ? 10 : col <= 20 ? 20 : 32; }
 void launch_finalize(Queue &, int, int, int, int) {}
 void finalize_flush(Queue &) {}
 void launch_publish(Queue &q, const double *src, double *dst, int count, unsigned long long seq,
@@ -266,9 +265,9 @@ void launch_cauchy_fix(Queue &q, const int64_t *list, int count, int64_t row0, i
 template <typename T>
 void launch_cauchy_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u, const int32_t *nbd, const T *g,
                         iw_t *iwhere, T *tbrk, WStore<T> w, int head, int col) {
-  const int MC = col == 0 ? 0 : maxc_for(col);
+  const auto S = CauchyScanSlots::of(col);
   double *res = q.d_res + q.res_off;
-  for (int k = 0; k < 2 * MC + 4; ++k) res[k] = 0.0;
+  for (int k = 0; k < S.nsum(); ++k) res[k] = 0.0;
   double bkmin = INF;
   for (int64_t i = 0; i < n; ++i) {
     const double xv = (double)x[i], lv = (double)l[i], uv = (double)u[i], gv = (double)g[i];
@@ -280,26 +279,26 @@ void launch_cauchy_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
       tb = -1.0, ng = 0.0;
     } else {
       ng = neggi;
-      res[2 * MC] = res[2 * MC] - neggi * neggi;
+      res[S.f1()] = res[S.f1()] - neggi * neggi;
       const double tl = nb <= 2 ? xv - lv : 0.0, tu = nb >= 2 ? uv - xv : 0.0;
       if (nb <= 2 && nb != 0 && neggi < 0.0) {
-        tb = tl / (-neggi), res[2 * MC + 1] += 1.0, bkmin = std::fmin(bkmin, tb);
+        tb = tl / (-neggi), res[S.nbreak()] += 1.0, bkmin = std::fmin(bkmin, tb);
       } else if (nb >= 2 && neggi > 0.0) {
-        tb = tu / neggi, res[2 * MC + 1] += 1.0, bkmin = std::fmin(bkmin, tb);
+        tb = tu / neggi, res[S.nbreak()] += 1.0, bkmin = std::fmin(bkmin, tb);
       } else {
-        tb = INF, res[2 * MC + 2] += 1.0;
-        if (std::fabs(neggi) > 0.0) res[2 * MC + 3] += 1.0;
+        tb = INF, res[S.nunb()] += 1.0;
+        if (std::fabs(neggi) > 0.0) res[S.nunbnz()] += 1.0;
       }
     }
     for (int j = 0; j < col; ++j) {
       const int64_t off = (int64_t)((head - 1 + j) % w.m) * w.ld + i;
-      res[j] += (double)w.wy[off] * ng;
-      res[MC + j] += (double)w.ws[off] * ng;
+      res[S.p_wy(j)] += (double)w.wy[off] * ng;
+      res[S.p_ws(j)] += (double)w.ws[off] * ng;
     }
     iwhere[i] = (iw_t)iw;
     tbrk[i] = (T)tb;
   }
-  res[2 * MC + 4] = bkmin;
+  res[S.bkmin()] = bkmin;
   q.launches++;
 }
 template <typename T>
