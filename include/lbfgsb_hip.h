@@ -390,6 +390,77 @@ int lbfgsb_hip_qn_apply(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v,
 int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out);
 
 /* -------------------------------------------------------------------------
+ * The active set, the bound multipliers and the projected gradient as device data.
+ * lbfgsb_hip_kkt is ONE pass over the caller's x, l, u, nbd, g (device pointers to this rank's n_local rows, of the
+ * context's real kind; 36 bytes per row in fp64) -- the arrays handed in, not the context's snapshot of the bounds.
+ * It needs no run on the context: only its stream, real kind, communicator and row0.  Per row i, in this order of
+ * precedence (the order of `active`, src/lbfgsb.f90:994-1028; codes as iwhere's, :348-355):
+ *   status  -1  nbd == 0 (unbounded)
+ *            3  nbd == 2 and u - l <= 0 (always fixed)
+ *            1  the row has a lower bound (nbd 1 or 2) and x <= l
+ *            2  the row has an upper bound (nbd 2 or 3) and x >= u
+ *            0  otherwise (free, bounded)
+ *   pg      the signed projected gradient: gi of projgr (:2610-2618) before the abs, by the device function
+ *           lbfgsb_hip_projgr's kernel uses.  REAL32: operands widened to double as there, the result rounded to fp32
+ *           on store.
+ *   mult    the signed bound multiplier (reduced cost): g on a status-3 row, g on a status-1 row when g > 0 (the
+ *           bound holds the row from below), g on a status-2 row when g < 0, +0 everywhere else.  A nonzero entry is
+ *           an exact copy of g.
+ * A bound that nbd says does not exist is never looked at (NaN in an unused l or u changes nothing).
+ * pg_out, mult_out (reals of the context's kind) and status_out (one byte per row) may each be NULL: that output is
+ * then neither computed into memory nor addressed.
+ * The summary is complete over all ranks and identical on each:
+ *   h_cnt[LBFGSB_KKT_N_UNBOUNDED .. LBFGSB_KKT_N_FIXED]  rows of status -1, 0, 1, 2, 3 (index = code + 1)
+ *   h_cnt[LBFGSB_KKT_N_BINDING]  status 1 with g > 0, or status 2 with g < 0
+ *   h_cnt[LBFGSB_KKT_N_WEAK]     status 1 or 2 and |g| <= tol (degenerate: active only weakly)
+ *   h_cnt[LBFGSB_KKT_N_LEAVING]  status 1 with g < -tol, or status 2 with g > tol (at a bound and wants to leave it)
+ *   h_cnt[LBFGSB_KKT_N_OUTSIDE]  the row has the bound and x < l or x > u strictly (a line-search step can leave the
+ *                                iterate an ulp outside the box)
+ *   h_val[LBFGSB_KKT_PG_MAX]     max |pg|: bit for bit what lbfgsb_hip_projgr returns on the same arrays, hence
+ *                                dsave(13) at a NEW_X or convergence return
+ *   h_val[LBFGSB_KKT_MULT_MAX]   max |mult|
+ *   h_val[LBFGSB_KKT_OUT_MAX]    the largest distance outside the box, max(l - x, x - u) over the bounds a row has
+ *                                (0 if no row is outside)
+ *   h_val[LBFGSB_KKT_GFREE_MAX]  max |g| over the rows of status -1 and 0
+ *
+ * lbfgsb_hip_kkt_list writes the GLOBAL 0-based indices (row0 + i) of this rank's rows whose status byte is selected,
+ * in ascending order, as device int64: bit (code + 1) of code_mask selects a code (0b01100: the rows at a lower or an
+ * upper bound; 0b00011: the free rows).  status is any device int8 array of n_local codes -1 .. 3 (other values
+ * select nothing); it need not come from lbfgsb_hip_kkt.  At most cap indices are written and nothing behind them is
+ * touched; *h_count is this rank's full count even when it exceeds cap (cap = 0 with idx_out = NULL: the counting
+ * call).  The order is deterministic: a stable compaction, no atomic hands out positions.  Per rank, not collective.
+ *
+ * Both are valid whenever no deferred line-search set-up is live and no built-in objective's value is still on the
+ * device: LBFGSB_E_STATE then, changing nothing.  LBFGSB_E_ARG: a NULL input or summary, tol negative or NaN,
+ * code_mask outside 0 .. 31, cap < 0, cap > 0 without idx_out.
+ * Calling them changes nothing a run computes: every return is bit-identical with or without the calls.
+ * Streams: as lbfgsb_hip_qn_apply -- the inputs are read on the context's stream; the summaries are host data, so the
+ * calls wait for that stream and the device outputs are complete at return.  Several ranks: lbfgsb_hip_kkt is called
+ * collectively, each rank with its own rows; the summary is reduced as the iteration's sums are (rank order / the
+ * host reducer).
+ * ------------------------------------------------------------------------- */
+#define LBFGSB_KKT_N_UNBOUNDED 0 /* h_cnt: status -1 */
+#define LBFGSB_KKT_N_FREE 1      /*        status  0 */
+#define LBFGSB_KKT_N_LOWER 2     /*        status  1 */
+#define LBFGSB_KKT_N_UPPER 3     /*        status  2 */
+#define LBFGSB_KKT_N_FIXED 4     /*        status  3 */
+#define LBFGSB_KKT_N_BINDING 5
+#define LBFGSB_KKT_N_WEAK 6
+#define LBFGSB_KKT_N_LEAVING 7
+#define LBFGSB_KKT_N_OUTSIDE 8
+#define LBFGSB_KKT_NCNT 9
+#define LBFGSB_KKT_PG_MAX 0 /* h_val */
+#define LBFGSB_KKT_MULT_MAX 1
+#define LBFGSB_KKT_OUT_MAX 2
+#define LBFGSB_KKT_GFREE_MAX 3
+#define LBFGSB_KKT_NVAL 4
+int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
+                   const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,
+                   double *h_val);
+int lbfgsb_hip_kkt_list(lbfgsb_hip_ctx *ctx, const int8_t *status, int code_mask, int64_t *idx_out, int64_t cap,
+                        int64_t *h_count);
+
+/* -------------------------------------------------------------------------
  * Per-kernel entry points (one per row of SURVEY.md 8a), for parity tests
  * and profiling.  All pointers are DEVICE pointers unless named h_*.
  * Reduction results come back in host doubles, already complete across

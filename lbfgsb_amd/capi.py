@@ -52,6 +52,8 @@ PROTOTYPES = {
     "lbfgsb_hip_export_state": (C.c_int, [_vp, _vp, _vp]),
     "lbfgsb_hip_qn_apply": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
     "lbfgsb_hip_qn_diag": (C.c_int, [_vp, C.c_int, _vp]),
+    "lbfgsb_hip_kkt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "lbfgsb_hip_kkt_list": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp]),
     "lbfgsb_hip_import_state": (C.c_int, [_vp, _vp, _vp, _vp]),
     "lbfgsb_hip_projgr": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lbfgsb_hip_wtv": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
@@ -91,6 +93,10 @@ PROTOTYPES = {
 
 E_NOGPU, E_ARG, E_ALLOC, E_COMM, E_STATE = -100, -101, -102, -103, -104   # status codes of include/lbfgsb_hip.h
 QN_B, QN_H = 0, 1  # lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag: the model B, its inverse H = B^-1
+# lbfgsb_hip_kkt: the slots of h_cnt and h_val (LBFGSB_KKT_* without the prefix, in index order) -- the field names
+# of solver.KktReport
+KKT_CNT = ("n_unbounded", "n_free", "n_lower", "n_upper", "n_fixed", "n_binding", "n_weak", "n_leaving", "n_outside")
+KKT_VAL = ("pg_max", "mult_max", "out_max", "gfree_max")
 F_REAL32 = 1
 F_MIRROR_INDEX = 2
 F_NO_RETURN_SYNC = 4

@@ -239,6 +239,21 @@ int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out) {
   return ctx->qn_diag(mode, out);
 }
 
+int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
+                   const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,
+                   double *h_val) {
+  if (!ctx || !x || !l || !u || !nbd || !g || !h_cnt || !h_val) return fail(LBFGSB_E_ARG, "kkt: NULL argument");
+  if (!(tol >= 0.0)) return fail(LBFGSB_E_ARG, "kkt: tol is negative or NaN");
+  return ctx->kkt(x, l, u, nbd, g, tol, pg_out, mult_out, status_out, h_cnt, h_val);
+}
+int lbfgsb_hip_kkt_list(lbfgsb_hip_ctx *ctx, const int8_t *status, int code_mask, int64_t *idx_out, int64_t cap,
+                        int64_t *h_count) {
+  if (!ctx || !status || !h_count) return fail(LBFGSB_E_ARG, "kkt_list: NULL argument");
+  if (code_mask < 0 || code_mask > 31) return fail(LBFGSB_E_ARG, "kkt_list: code_mask has bits beyond the five codes");
+  if (cap < 0 || (cap > 0 && !idx_out)) return fail(LBFGSB_E_ARG, "kkt_list: cap < 0, or cap > 0 without idx_out");
+  return ctx->kkt_list(status, code_mask, idx_out, cap, h_count);
+}
+
 int lbfgsb_hip_projgr(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u,
                       const int32_t *nbd, const void *g, double *h_sbgnrm) {
   if (!ctx || !x || !l || !u || !nbd || !g || !h_sbgnrm) return fail(LBFGSB_E_ARG, "projgr: NULL argument");

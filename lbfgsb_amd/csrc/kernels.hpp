@@ -541,4 +541,22 @@ template <typename T>
 hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int col, const double *np, double alpha,
                           T *out);
 
+// ---- the active-set report (k_kkt.hip, solver_kkt.inl) ----
+// One pass over the caller's x, l, u, nbd, g: per row the status (iwhere codes), the signed projected gradient and the
+// bound multiplier into whichever of status / pg / mult is not NULL, and the KktSlots sums and maxima: partials into
+// part ([slot][MAX_BLOCKS]), then a fixed-order finalize into res[0 .. KktSlots::size()).  Buffers of the caller's
+// own; the Queue is read for its stream only.
+template <typename T>
+hipError_t launch_kkt(const Queue &q, int64_t n, const T *x, const T *l, const T *u, const int32_t *nbd, const T *g,
+                      double tol, T *pg, T *mult, int8_t *status, double *part, double *res);
+// The rows whose status byte is selected by code_mask (bit code + 1, codes -1 .. 3), ascending, as row0 + i into
+// idx[0 .. min(count, cap)): count per chunk of KKT_LIST_CHUNK rows, scan of the chunk totals, write.  tmp holds
+// kkt_list_chunks(n) + 1 counts; tmp[kkt_list_chunks(n)] is the full count afterwards.  idx == nullptr or cap == 0:
+// the count alone.
+constexpr int KKT_LIST_STEPS = 16;                          // rows per lane
+constexpr int KKT_LIST_CHUNK = BLOCK * KKT_LIST_STEPS;      // rows per workgroup
+inline int64_t kkt_list_chunks(int64_t n) { return (n + KKT_LIST_CHUNK - 1) / KKT_LIST_CHUNK; }
+hipError_t launch_kkt_list(const Queue &q, int64_t n, int64_t row0, const int8_t *status, int code_mask, int64_t *idx,
+                           int64_t cap, int64_t *tmp);
+
 }  // namespace lbk

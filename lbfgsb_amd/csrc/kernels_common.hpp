@@ -424,7 +424,8 @@ __device__ __forceinline__ void dict_apply(const T (&tab)[16], int ub, int (&nb)
 }
 
 // ---- projgr (:2594-2622) of one row ----
-__device__ __forceinline__ double proj_g(double x, double l, double u, int nb, double gi) {
+// the signed projected gradient (gi of :2610-2618 before the abs; what lbfgsb_hip_kkt stores) ...
+__device__ __forceinline__ double proj_g_signed(double x, double l, double u, int nb, double gi) {
   if (nb != 0) {
     if (gi < 0.0) {
       if (nb >= 2) gi = fmax(x - u, gi);
@@ -432,7 +433,11 @@ __device__ __forceinline__ double proj_g(double x, double l, double u, int nb, d
       if (nb <= 2) gi = fmin(x - l, gi);
     }
   }
-  return fabs(gi);
+  return gi;
+}
+// ... and its magnitude, the term of sbgnrm
+__device__ __forceinline__ double proj_g(double x, double l, double u, int nb, double gi) {
+  return fabs(proj_g_signed(x, l, u, nb, gi));
 }
 
 // ---- ordering of breakpoints ----

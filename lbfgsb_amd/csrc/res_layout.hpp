@@ -90,6 +90,25 @@ struct UpdScanSlots {  // mc = maxc_stride(col - 1)
 // the storing pass (subsm_update_kernel, the last tile of the m > 32 r pass): three sums and a minimum
 enum SubsmSlot { SUBSM_IWORD = 0, SUBSM_DDP = 1, SUBSM_DTD = 2, SUBSM_STPMX = 3, SUBSM_NSUM = 3, SUBSM_SIZE = 4 };
 
+// the active-set report (kkt_kernel, lbfgsb_hip_kkt): nine counts, then four maxima, in the order of the header's
+// LBFGSB_KKT_* indices (cnt(k) is h_cnt[k], val(k) is h_val[k])
+struct KktSlots {
+  static constexpr int NCNT = 9, NVAL = 4;
+  static constexpr int status(int code) { return code + 1; }  // rows of status -1 .. 3
+  static constexpr int binding() { return 5; }
+  static constexpr int weak() { return 6; }
+  static constexpr int leaving() { return 7; }
+  static constexpr int outside() { return 8; }
+  static constexpr int cnt(int k) { return k; }
+  static constexpr int nsum() { return NCNT; }
+  static constexpr int pg_max() { return nsum() + 0; }     // max |proj g|: projgr's slot
+  static constexpr int mult_max() { return nsum() + 1; }   // max |multiplier|
+  static constexpr int out_max() { return nsum() + 2; }    // largest distance outside the box
+  static constexpr int gfree_max() { return nsum() + 3; }  // max |g| over the rows of status -1 and 0
+  static constexpr int val(int k) { return nsum() + k; }
+  static constexpr int size() { return nsum() + NVAL; }
+};
+
 constexpr int RES_MAX = 8 * MAXM + 16;  // rows of the partial-sum matrix, doubles of d_res for one phase
 static_assert(RES_MAX >= UpdScanSlots{MAXM, true}.size() && RES_MAX >= CmprlbWtvSlots{MAXM, true}.size(), "RES_MAX");
 // update pass with formk's new-row sums at col - 1 > 20 (k_update.hip, "the split pass"): several launches of the

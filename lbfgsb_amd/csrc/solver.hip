@@ -157,6 +157,7 @@ class Solver final : public lbfgsb_hip_ctx {
 
   void release() {
     qn_release();
+    kkt_release();
     if (debug_walk && n_mid > 0)
       std::fprintf(stderr, "[host] %lld stretches, us each: linesearch+return %.1f | caller %.1f | update %.1f | "
                            "cauchy+freev %.1f | formk+subsm algebra %.1f | all %.1f\n",
@@ -1928,6 +1929,7 @@ class Solver final : public lbfgsb_hip_ctx {
 #include "solver_state.inl"     // state exchange, per-kernel doors, communicators
 #include "solver_doors.inl"     // routine doors (active, errclb, cauchy, freev, formk, cmprlb, subsm, lnsrlb, matupd)
 #include "solver_qn.inl"        // the curvature model B, H = B^-1 as device operators (qn_apply, qn_diag)
+#include "solver_kkt.inl"       // the active set, the multipliers and the projected gradient (kkt, kkt_list)
 };
 
 }  // namespace

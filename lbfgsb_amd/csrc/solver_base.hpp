@@ -156,6 +156,11 @@ struct lbfgsb_hip_ctx {
   // the curvature model of the last return as a device operator (solver_qn.inl, lbfgsb_hip_qn_apply / qn_diag)
   virtual int qn_apply(int mode, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) = 0;
   virtual int qn_diag(int mode, void *out) = 0;
+  // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
+  // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
+  virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,
+                  void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt, double *h_val) = 0;
+  virtual int kkt_list(const int8_t *status, int code_mask, int64_t *idx_out, int64_t cap, int64_t *h_count) = 0;
   // communicators (capi.hip): an initialised RCCL communicator / a host reducer for this context
   virtual int attach_rccl(ncclComm_t comm, int rank, int nranks) = 0;
   virtual ncclComm_t rccl_comm() const = 0;

@@ -45,6 +45,15 @@
       public :: lbfgsb_qn_apply, lbfgsb_qn_diag        ! the curvature model B, H = B^-1 of the last return on the
                                                        ! device (lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag)
       integer,parameter,public :: LBFGSB_QN_B = 0, LBFGSB_QN_H = 1
+      public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
+                                                       ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
+      ! slots of lbfgsb_kkt's cnt(:) and val(:): the header's LBFGSB_KKT_* indices + 1 (Fortran arrays start at 1)
+      integer,parameter,public :: LBFGSB_KKT_NCNT = 9, LBFGSB_KKT_NVAL = 4
+      integer,parameter,public :: LBFGSB_KKT_N_UNBOUNDED = 1, LBFGSB_KKT_N_FREE = 2, LBFGSB_KKT_N_LOWER = 3,       &
+                                  LBFGSB_KKT_N_UPPER = 4, LBFGSB_KKT_N_FIXED = 5, LBFGSB_KKT_N_BINDING = 6,        &
+                                  LBFGSB_KKT_N_WEAK = 7, LBFGSB_KKT_N_LEAVING = 8, LBFGSB_KKT_N_OUTSIDE = 9
+      integer,parameter,public :: LBFGSB_KKT_PG_MAX = 1, LBFGSB_KKT_MULT_MAX = 2, LBFGSB_KKT_OUT_MAX = 3,          &
+                                  LBFGSB_KKT_GFREE_MAX = 4
       ! flags of lbfgsb_create (include/lbfgsb_hip.h)
       integer,parameter,public :: LBFGSB_F_REAL32 = 1, LBFGSB_F_MIRROR_INDEX = 2, LBFGSB_F_NO_RETURN_SYNC = 4, &
                                   LBFGSB_F_PARALLEL_GCP = 8, LBFGSB_F_INDEX_TIES = 32, LBFGSB_F_DEFER_LNSRCH = 64
@@ -146,6 +155,22 @@
             integer(c_int),value :: mode
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_diag
+         function lbfgsb_hip_kkt(ctx,x,l,u,nbd,g,tol,pg,mult,status,cnt,val) bind(C,name='lbfgsb_hip_kkt') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, x, l, u, nbd, g, pg, mult, status
+            real(c_double),value :: tol
+            integer(c_int64_t) :: cnt(9)
+            real(c_double) :: val(4)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_kkt
+         function lbfgsb_hip_kkt_list(ctx,status,code_mask,idx,cap,count) bind(C,name='lbfgsb_hip_kkt_list') result(rc)
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, status, idx
+            integer(c_int),value :: code_mask
+            integer(c_int64_t),value :: cap
+            integer(c_int64_t) :: count
+            integer(c_int) :: rc
+         end function lbfgsb_hip_kkt_list
          function c_strlen(s) bind(C,name='strlen') result(k)
             import :: c_ptr, c_size_t
             type(c_ptr),value :: s
@@ -402,6 +427,35 @@
       integer,intent(out) :: rc
       rc = lbfgsb_hip_qn_diag(ctx, int(mode, c_int), out)
       end subroutine lbfgsb_qn_diag
+
+      ! The active set, the multipliers and the projected gradient (include/lbfgsb_hip.h, "The active set, the bound
+      ! multipliers and the projected gradient as device data"): one pass over the device arrays x, l, u, nbd, g of
+      ! the context's real kind (nbd: int32).  pg, mult (reals) and status (one byte per row, iwhere's codes -1 .. 3)
+      ! are device buffers or c_null_ptr (that output is then left out).  cnt(LBFGSB_KKT_N_*) and val(LBFGSB_KKT_*)
+      ! are host arrays, complete over all ranks.  rc as the C entry returns it.
+      subroutine lbfgsb_kkt(ctx, x, l, u, nbd, g, tol, pg, mult, status, cnt, val, rc)
+      type(c_ptr),intent(in) :: ctx, x, l, u, nbd, g, pg, mult, status
+      real(c_double),intent(in) :: tol
+      integer(c_int64_t),intent(out) :: cnt(LBFGSB_KKT_NCNT)
+      real(c_double),intent(out) :: val(LBFGSB_KKT_NVAL)
+      integer,intent(out) :: rc
+      cnt = 0_c_int64_t
+      val = 0.0_c_double
+      rc = lbfgsb_hip_kkt(ctx, x, l, u, nbd, g, tol, pg, mult, status, cnt, val)
+      end subroutine lbfgsb_kkt
+
+      ! The rows whose status byte is selected by code_mask (bit code + 1; e.g. 12 = at a lower or an upper bound),
+      ! ascending, as GLOBAL 0-based int64 indices (row0 + i) into the device buffer idx: at most cap of them, count
+      ! receives this rank's full count.  idx = c_null_ptr with cap = 0 is the counting call.
+      subroutine lbfgsb_kkt_list(ctx, status, code_mask, idx, cap, count, rc)
+      type(c_ptr),intent(in) :: ctx, status, idx
+      integer,intent(in) :: code_mask
+      integer(c_int64_t),intent(in) :: cap
+      integer(c_int64_t),intent(out) :: count
+      integer,intent(out) :: rc
+      count = 0_c_int64_t
+      rc = lbfgsb_hip_kkt_list(ctx, status, int(code_mask, c_int), idx, cap, count)
+      end subroutine lbfgsb_kkt_list
 
       function lbfgsb_error_message() result(msg)
       character(len=:),allocatable :: msg

@@ -383,6 +383,61 @@ class DeviceSolver:
         """H (default) or B as a small linear-operator object: hess_inv = sol.qn_operator() after minimize()."""
         return QnOperator(self, inverse)
 
+    # ---- the active set, the multipliers and the projected gradient (include/lbfgsb_hip.h, lbfgsb_hip_kkt) ----
+    def kkt(self, x, l, u, nbd, g, tol: float = 0.0, pg=True, mult=True, status=True) -> "KktReport":
+        """One pass over x, l, u, nbd, g (device tensors of this rank's rows): the report of include/lbfgsb_hip.h's
+        "active set" block.  pg / mult / status: True allocates that per-row output, a tensor is written in place,
+        False / None leaves it out (it then costs nothing).  The summary is complete over all ranks."""
+        import torch
+        want = torch.float32 if self.real == np.float32 else torch.float64
+        for name, t in (("x", x), ("l", l), ("u", u), ("g", g)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == want and t.dim() == 1
+                    and t.numel() >= self.n and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous CUDA tensor of dtype %s with n = %d rows"
+                                % (name, want, self.n))
+        if not (isinstance(nbd, torch.Tensor) and nbd.is_cuda and nbd.dtype == torch.int32 and nbd.dim() == 1
+                and nbd.numel() >= self.n and nbd.is_contiguous()):
+            raise TypeError("nbd must be a contiguous int32 CUDA tensor with n = %d rows" % self.n)
+
+        def out_of(o, dt, name):
+            if o is None or o is False:
+                return None
+            if o is True:
+                return torch.empty(self.n, dtype=dt, device=x.device)
+            if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == dt and o.dim() == 1
+                    and o.numel() >= self.n and o.is_contiguous()):
+                raise TypeError("%s must be a contiguous CUDA tensor of dtype %s with n = %d rows"
+                                % (name, dt, self.n))
+            return o
+        pg, mult, status = out_of(pg, want, "pg"), out_of(mult, want, "mult"), out_of(status, torch.int8, "status")
+        cnt = np.zeros(len(capi.KKT_CNT), np.int64)
+        val = np.zeros(len(capi.KKT_VAL), np.float64)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_kkt(self.h, _p(x), _p(l), _p(u), _p(nbd), _p(g), float(tol), _p(pg), _p(mult),
+                                      _p(status), _p(cnt), _p(val)))
+        return KktReport(cnt, val, float(tol), pg, mult, status)
+
+    def kkt_indices(self, status, codes):
+        """The global 0-based indices (row0 + i) of this rank's rows whose status byte is one of `codes` (an int or
+        an iterable of the codes -1 .. 3), ascending, as an int64 tensor of exactly the count's length
+        (lbfgsb_hip_kkt_list: a counting call, then the list).  status: an int8 CUDA tensor of n codes."""
+        import torch
+        if not (isinstance(status, torch.Tensor) and status.is_cuda and status.dtype == torch.int8
+                and status.dim() == 1 and status.numel() >= self.n and status.is_contiguous()):
+            raise TypeError("status must be a contiguous int8 CUDA tensor with n = %d rows" % self.n)
+        mask = 0
+        for c in ([codes] if isinstance(codes, (int, np.integer)) else codes):
+            if not -1 <= int(c) <= 3:
+                raise ValueError("status codes are -1 .. 3")
+            mask |= 1 << (int(c) + 1)
+        count = np.zeros(1, np.int64)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_kkt_list(self.h, _p(status), mask, None, 0, _p(count)))
+        idx = torch.empty(int(count[0]), dtype=torch.int64, device=status.device)
+        if count[0] > 0:
+            check(self.lib.lbfgsb_hip_kkt_list(self.h, _p(status), mask, _p(idx), int(count[0]), _p(count)))
+        return idx
+
     def projgr(self, x, l, u, nbd, g) -> float:
         out = np.zeros(1)
         check(self.lib.lbfgsb_hip_projgr(self.h, _p(x), _p(l), _p(u), _p(nbd), _p(g), _p(out)))
@@ -609,6 +664,25 @@ class DeviceSolver:
         return dict(launches=a.value, syncs=b.value, cauchy_fullsorts=c.value, wait_seconds=w.value,
                     collectives=nc.value, collective_bytes=nb.value, freev_skipped=fs.value,
                     skip_scans_reused=sr.value, refreshes=rf.value)
+
+
+class KktReport:
+    """What DeviceSolver.kkt returns: the counts and values of lbfgsb_hip_kkt by name (capi.KKT_CNT, capi.KKT_VAL --
+    the header's LBFGSB_KKT_* in lower case), the raw arrays as `counts` / `values`, `tol`, and the per-row tensors that
+    were asked for (`pg`, `mult`, `status`; None otherwise)."""
+
+    def __init__(self, counts, values, tol, pg, mult, status):
+        self.counts, self.values, self.tol = counts, values, tol
+        self.pg, self.mult, self.status = pg, mult, status
+        for k, name in enumerate(capi.KKT_CNT):
+            setattr(self, name, int(counts[k]))
+        for k, name in enumerate(capi.KKT_VAL):
+            setattr(self, name, float(values[k]))
+
+    def __repr__(self):
+        return "KktReport(%s)" % ", ".join(
+            ["%s=%d" % (k, getattr(self, k)) for k in capi.KKT_CNT]
+            + ["%s=%r" % (k, getattr(self, k)) for k in capi.KKT_VAL])
 
 
 class QnOperator:
