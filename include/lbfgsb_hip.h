@@ -382,12 +382,43 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  * sums on the host once per 4 vectors.  Several ranks: every rank calls collectively with its own rows; the sums
  * are reduced as the iteration's (rank order / the host reducer), so every rank uses the same coefficients.
  * REAL32 contexts: v and out are fp32, every sum fp64.
+ *
+ * Square roots, log-determinants and draws.  Both models are A = alpha I + [S, Y] N [S, Y]' (alpha = theta for B,
+ * 1 / theta for H), so with G = [S, Y]'[S, Y], P = G^(1/2) and P N P = V diag(delta) V'
+ *   A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]',
+ *   C = N / (2 sqrt(alpha)) - (N P V) diag(1 / (2 sqrt(alpha) (sqrt(alpha) + sqrt(alpha + delta_i))^2)) (N P V)'
+ *   log det A = n_global log alpha + sum_i log1p(delta_i / alpha)
+ * -- the symmetric square root, from two symmetric eigenproblems of order 2col on the host (a cyclic Jacobi in a
+ * fixed order: the same bits on every rank), once per set of pairs; G comes from Ss and the Gram pass above.  At
+ * most LBFGSB_QN_ROOT_MAXCOL stored pairs (LBFGSB_E_ARG beyond); LBFGSB_E_STATE when alpha + delta_i < -1e-8 alpha
+ * (the model is not positive definite).
+ *   qn_apply with LBFGSB_QN_B_SQRT / LBFGSB_QN_H_SQRT: out_j = A^(1/2) v_j, everything else as for B / H (qn_diag
+ *     takes no root mode: LBFGSB_E_ARG).  The modes 2 and 3 stay invalid, as they were.
+ *   qn_logdet: *h_logdet = log det A over all n_global rows, the same value on every rank (collective on several
+ *     ranks, as qn_apply); no stored pair: +- n_global log theta.
+ *   qn_draw: out_j = mean + scale A^(1/2) z_(first + j), j < k, result j at out + j*ldo: a draw from N(mean,
+ *     scale^2 A) (mode LBFGSB_QN_B or LBFGSB_QN_H names the covariance A).  mean (n_local reals) may be NULL; it is
+ *     read once per sample and may not overlap out.  The standard normal z_s is generated inside the two passes over
+ *     W and never stored.  Entry i of z_s is a function of (seed, the global row row0 + i, s) and nothing else -- not
+ *     of the sharding, k, the launch shape or the layout of W: Philox4x32-10 (Random123 constants) with counter (row
+ *     lo, row hi, pair lo, pair hi), pair = s >> 1, key (seed lo, seed hi); from the output words a = w0 2^32 + w1,
+ *     b = w2 2^32 + w3: u = ((a >> 12) + 0.5) 2^-52, v = (b >> 12) 2^-52, r = sqrt(-2 log u); an even s takes
+ *     r cospi(2v), an odd one r sinpi(2v).  REAL32 contexts: z and all arithmetic in fp64, rounded on store.
+ * When, streams and refusals are qn_apply's.  LBFGSB_E_ARG in addition: NULL out / h_logdet, k < 1, first < 0,
+ * ldo < n_local, a mode other than B / H, a scale that is not finite.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
+#define LBFGSB_QN_SQRT 4   /* qn_apply only, added to LBFGSB_QN_B / LBFGSB_QN_H: the symmetric square root */
+#define LBFGSB_QN_B_SQRT (LBFGSB_QN_SQRT | LBFGSB_QN_B) /* 4: out = B^(1/2) v */
+#define LBFGSB_QN_H_SQRT (LBFGSB_QN_SQRT | LBFGSB_QN_H) /* 5: out = H^(1/2) v */
+#define LBFGSB_QN_ROOT_MAXCOL 64
 int lbfgsb_hip_qn_apply(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, void *out,
                         int64_t ldo);
 int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out);
+int lbfgsb_hip_qn_logdet(lbfgsb_hip_ctx *ctx, int mode, double *h_logdet);
+int lbfgsb_hip_qn_draw(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first, const void *mean,
+                       double scale, void *out, int64_t ldo);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.

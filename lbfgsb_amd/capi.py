@@ -52,6 +52,9 @@ PROTOTYPES = {
     "lbfgsb_hip_export_state": (C.c_int, [_vp, _vp, _vp]),
     "lbfgsb_hip_qn_apply": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
     "lbfgsb_hip_qn_diag": (C.c_int, [_vp, C.c_int, _vp]),
+    "lbfgsb_hip_qn_logdet": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),
+    "lbfgsb_hip_qn_draw": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_uint64, C.c_int64, _vp, C.c_double, _vp,
+                                     C.c_int64]),
     "lbfgsb_hip_kkt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "lbfgsb_hip_kkt_list": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp]),
     "lbfgsb_hip_import_state": (C.c_int, [_vp, _vp, _vp, _vp]),
@@ -93,6 +96,8 @@ PROTOTYPES = {
 
 E_NOGPU, E_ARG, E_ALLOC, E_COMM, E_STATE = -100, -101, -102, -103, -104   # status codes of include/lbfgsb_hip.h
 QN_B, QN_H = 0, 1  # lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag: the model B, its inverse H = B^-1
+QN_B_SQRT, QN_H_SQRT = 4, 5  # lbfgsb_hip_qn_apply only: the symmetric square roots B^(1/2), H^(1/2)
+QN_ROOT_MAXCOL = 64
 # lbfgsb_hip_kkt: the slots of h_cnt and h_val (LBFGSB_KKT_* without the prefix, in index order) -- the field names
 # of solver.KktReport
 KKT_CNT = ("n_unbounded", "n_free", "n_lower", "n_upper", "n_fixed", "n_binding", "n_weak", "n_leaving", "n_outside")

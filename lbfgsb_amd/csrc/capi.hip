@@ -229,7 +229,8 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
 int lbfgsb_hip_qn_apply(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, void *out,
                         int64_t ldo) {
   if (!ctx || !v || !out) return fail(LBFGSB_E_ARG, "qn_apply: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_apply: mode");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H && mode != LBFGSB_QN_B_SQRT && mode != LBFGSB_QN_H_SQRT)
+    return fail(LBFGSB_E_ARG, "qn_apply: mode");
   if (k < 1 || ldv < ctx->n || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_apply: k < 1 or ld < n_local");
   return ctx->qn_apply(mode, k, v, ldv, out, ldo);
 }
@@ -237,6 +238,19 @@ int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out) {
   if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_diag: NULL argument");
   if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_diag: mode");
   return ctx->qn_diag(mode, out);
+}
+int lbfgsb_hip_qn_logdet(lbfgsb_hip_ctx *ctx, int mode, double *h_logdet) {
+  if (!ctx || !h_logdet) return fail(LBFGSB_E_ARG, "qn_logdet: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_logdet: mode");
+  return ctx->qn_logdet(mode, h_logdet);
+}
+int lbfgsb_hip_qn_draw(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first, const void *mean,
+                       double scale, void *out, int64_t ldo) {
+  if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_draw: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_draw: mode");
+  if (k < 1 || first < 0 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_draw: k < 1, first < 0 or ldo < n_local");
+  if (!std::isfinite(scale)) return fail(LBFGSB_E_ARG, "qn_draw: scale is not finite");
+  return ctx->qn_draw(mode, k, seed, first, mean, scale, out, ldo);
 }
 
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,

@@ -222,6 +222,128 @@ inline void qn_pack_n(int col, int mc, const double *nm, double *np) {
     }
 }
 
+// ---- the square root and the log-determinant of the model (lbfgsb_hip_qn_apply's root modes, qn_logdet, qn_draw) ----
+// Both models are A = alpha I + W N W' with W = [S, Y] and G = W'W.  With P = G^(1/2) and P N P = V diag(delta) V'
+// (delta: the non-zero eigenvalues of W N W'),
+//   A^(1/2) = sqrt(alpha) I + W C W',
+//   C = N / (2 sqrt(alpha)) - (N P V) diag(1 / (2 sqrt(alpha) (sqrt(alpha) + sqrt(alpha + delta_i))^2)) (N P V)'
+//   log det A = n log alpha + sum_i log1p(delta_i / alpha)
+// -- symmetric eigenproblems only, and no division by G (nearly parallel pairs cost nothing).  The columns of W are
+// scaled to unit length first (W D^-1, D N D, D = diag(G)^(1/2): the same A): the pairs of a converging run shrink
+// by many orders of magnitude while N grows as their inverse, and the eigensolver's absolute accuracy would
+// otherwise be spent on the largest columns alone.
+
+// Cyclic Jacobi for a symmetric matrix of order d (column-major, leading dimension d; a is destroyed): eigenvalues
+// into w, eigenvectors into the columns of v.  Fixed sweep order (p < q, row by row), so the same input gives the
+// same bits everywhere.  Returns the number of sweeps, or -1 when 60 sweeps did not converge.
+inline int jacobi_eig(int d, double *a, double *v, double *w) {
+  for (int j = 0; j < d; ++j)
+    for (int i = 0; i < d; ++i) v[i + (size_t)j * d] = i == j ? 1.0 : 0.0;
+  double fro = 0.0;
+  for (int k = 0; k < d * d; ++k) fro = fro + a[k] * a[k];
+  const double tiny = 1e-18 * std::sqrt(fro);  // entries below this no longer move an eigenvalue in fp64
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    int rotated = 0;
+    for (int p = 0; p < d - 1; ++p)
+      for (int q = p + 1; q < d; ++q) {
+        const double apq = a[p + (size_t)q * d];
+        if (std::fabs(apq) <= tiny) {
+          a[p + (size_t)q * d] = a[q + (size_t)p * d] = 0.0;
+          continue;
+        }
+        ++rotated;
+        const double app = a[p + (size_t)p * d], aqq = a[q + (size_t)q * d];
+        const double th = (aqq - app) / (2.0 * apq);
+        const double t = (th >= 0.0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < d; ++k) {  // columns p, q of a J
+          const double akp = a[k + (size_t)p * d], akq = a[k + (size_t)q * d];
+          a[k + (size_t)p * d] = c * akp - s * akq;
+          a[k + (size_t)q * d] = s * akp + c * akq;
+        }
+        for (int k = 0; k < d; ++k) {  // rows p, q of J' (a J)
+          const double apk = a[p + (size_t)k * d], aqk = a[q + (size_t)k * d];
+          a[p + (size_t)k * d] = c * apk - s * aqk;
+          a[q + (size_t)k * d] = s * apk + c * aqk;
+        }
+        a[p + (size_t)q * d] = a[q + (size_t)p * d] = 0.0;
+        for (int k = 0; k < d; ++k) {
+          const double vkp = v[k + (size_t)p * d], vkq = v[k + (size_t)q * d];
+          v[k + (size_t)p * d] = c * vkp - s * vkq;
+          v[k + (size_t)q * d] = s * vkp + c * vkq;
+        }
+      }
+    if (!rotated) {
+      for (int i = 0; i < d; ++i) w[i] = a[i + (size_t)i * d];
+      return sweep;
+    }
+  }
+  return -1;
+}
+
+// C (d x d, d = 2col, column-major, symmetric) and sum_i log1p(delta_i / alpha) from the Gram g = W'W and the
+// symmetric n_ of the model (both d x d).  work: 6 d^2 + d doubles.  Returns 0, -1 (the eigensolver did not
+// converge) or -2 (alpha + delta_i < -1e-8 alpha: the model is not positive definite).
+inline int qn_root(int d, double alpha, const double *g, const double *n_, double *cm, double *logsum, double *work) {
+  *logsum = 0.0;
+  if (d == 0) return 0;
+  const size_t dd = (size_t)d * d;
+  double *a = work, *u = work + dd, *p = work + 2 * dd, *t = work + 3 * dd, *x = work + 4 * dd, *w = work + 5 * dd;
+  auto at = [d](double *m, int i, int j) -> double & { return m[i + (size_t)j * d]; };
+  auto mul = [&](const double *l, const double *r, double *o) {  // o = l r
+    for (int j = 0; j < d; ++j)
+      for (int i = 0; i < d; ++i) {
+        double s = 0.0;
+        for (int k = 0; k < d; ++k) s = s + l[i + (size_t)k * d] * r[k + (size_t)j * d];
+        o[i + (size_t)j * d] = s;
+      }
+  };
+  // unit columns: G <- D^-1 G D^-1 (in a), N <- D N D (in t, then nn), C <- D^-1 C D^-1 at the end
+  double *ds = cm;  // (cm is written last: its first d entries hold D until then)
+  for (int i = 0; i < d; ++i) ds[i] = g[i + (size_t)i * d] > 0.0 ? std::sqrt(g[i + (size_t)i * d]) : 1.0;
+  for (int j = 0; j < d; ++j)
+    for (int i = 0; i < d; ++i) {
+      at(a, i, j) = g[i + (size_t)j * d] / (ds[i] * ds[j]);
+      at(t, i, j) = 0.5 * (n_[i + (size_t)j * d] + n_[j + (size_t)i * d]) * (ds[i] * ds[j]);
+    }
+  // P = U max(Lambda, 0)^(1/2) U'
+  if (jacobi_eig(d, a, u, w) < 0) return -1;
+  for (int j = 0; j < d; ++j) {
+    const double r = std::sqrt(std::max(w[j], 0.0));
+    for (int i = 0; i < d; ++i) at(x, i, j) = at(u, i, j) * r;
+  }
+  for (int j = 0; j < d; ++j)
+    for (int i = 0; i <= j; ++i) {
+      double s = 0.0;
+      for (int k = 0; k < d; ++k) s = s + at(x, i, k) * at(u, j, k);
+      at(p, i, j) = at(p, j, i) = s;
+    }
+  // T = P N P, symmetrised = V diag(delta) V'
+  double *nn = work + 5 * dd + d;  // the scaled N
+  for (size_t k = 0; k < dd; ++k) nn[k] = t[k];
+  mul(nn, p, x);  // x = N P
+  mul(p, x, t);
+  for (int j = 0; j < d; ++j)
+    for (int i = 0; i < j; ++i) at(t, i, j) = at(t, j, i) = 0.5 * (at(t, i, j) + at(t, j, i));
+  if (jacobi_eig(d, t, u, w) < 0) return -1;  // u = V, w = delta
+  mul(x, u, a);                               // a = N P V
+  const double ra = std::sqrt(alpha);
+  for (int i = 0; i < d; ++i) {
+    if (alpha + w[i] < -1e-8 * alpha) return -2;
+    const double rs = ra + std::sqrt(std::max(alpha + w[i], 0.0));
+    *logsum = *logsum + std::log1p(std::max(w[i], -alpha) / alpha);
+    w[i] = 1.0 / (2.0 * ra * (rs * rs));
+  }
+  for (int i = 0; i < d; ++i) u[i] = ds[i];  // (V is used up; cm is written from here on)
+  for (int j = 0; j < d; ++j)
+    for (int i = 0; i <= j; ++i) {
+      double s = 0.0;
+      for (int k = 0; k < d; ++k) s = s + at(a, i, k) * w[k] * at(a, j, k);
+      at(cm, i, j) = at(cm, j, i) = (at(nn, i, j) / (2.0 * ra) - s) / (u[i] * u[j]);
+    }
+  return 0;
+}
+
 // ---- 60-byte blank padded strings (Fortran character(len=60)) ----
 inline void str60_set(char *t, const char *s) {
   size_t k = std::strlen(s);

@@ -11,15 +11,9 @@
 // 16 (qn_wtv, qn_expand: any number of pairs) or all at once up to 32 (qn_diag).  Reductions: per-lane fp64
 // accumulators -> block_reduce_store -> one partial per workgroup -> qn_finalize in a fixed order, into buffers of
 // the operator's own (never the iteration's q.d_part / q.d_res).  Nothing here touches the Queue's counters.
-#include "kernels_common.hpp"
+#include "k_qn_common.hpp"
 
 namespace lbk {
-
-template <bool CW>
-__device__ __forceinline__ int64_t qn_slot(const uint64_t *__restrict__ lmask, int64_t i) {
-  if constexpr (CW) return wrow(lmask, i);
-  else return i;
-}
 
 // sums: slot kk * 2MC + j = S(:, c0 + j)' v_kk, slot kk * 2MC + MC + j = Y(:, c0 + j)' v_kk (j >= col - c0: zero).
 // VSLOT: vector row i is read at the SLOT of row i (the vectors are columns of W themselves: the Gram).
@@ -149,76 +143,14 @@ __global__ __launch_bounds__(BLOCK) void qn_diag_kernel(int64_t n, const T *__re
   });
 }
 
-// ---------------------------------------------------------------- launches
-namespace {
-template <typename T>
-bool aligned_for(const T *p, int v) {
-  return ((uintptr_t)p % ((uintptr_t)v * sizeof(T))) == 0;
-}
-}  // namespace
-
+// ---------------------------------------------------------------- launches (dispatch: k_qn_common.hpp)
 int qn_mc(int ncols) { return ncols <= 5 ? 5 : (ncols <= 10 ? 10 : QN_TILE); }
 int qn_kmax(int mc) { return mc <= 10 ? 4 : 2; }
 
-#define QN_DISPATCH_MC(mc, ...)   \
-  do {                            \
-    if ((mc) == 5) {              \
-      constexpr int MC = 5;       \
-      __VA_ARGS__;                \
-    } else if ((mc) == 10) {      \
-      constexpr int MC = 10;      \
-      __VA_ARGS__;                \
-    } else {                      \
-      constexpr int MC = QN_TILE; \
-      __VA_ARGS__;                \
-    }                             \
-  } while (0)
-#define QN_DISPATCH_K(k, ...)                 \
-  do {                                        \
-    if ((k) == 1) {                           \
-      constexpr int K = 1;                    \
-      __VA_ARGS__;                            \
-    } else if ((k) == 2) {                    \
-      constexpr int K = 2;                    \
-      __VA_ARGS__;                            \
-    } else if constexpr (MC <= 10) {          \
-      constexpr int K = 4;                    \
-      __VA_ARGS__;                            \
-    }                                         \
-  } while (0)
-#define QN_DISPATCH_BOOL(c, NAME, ...) \
-  do {                                 \
-    if (c) {                           \
-      constexpr bool NAME = true;      \
-      __VA_ARGS__;                     \
-    } else {                           \
-      constexpr bool NAME = false;     \
-      __VA_ARGS__;                     \
-    }                                  \
-  } while (0)
-// the tile-local layout exists for fp64 and m <= 10 only (Solver::cw_eligible): no other CW instantiation.  A layout
-// handed to any other combination launches nothing (the caller reports hipErrorInvalidValue): never natural-order
-// reads of a permuted W
-#define QN_DISPATCH_CW(lm, ...)                                 \
-  do {                                                          \
-    if constexpr (sizeof(T) == 8 && MC <= 10) {                 \
-      if (lm) {                                                 \
-        constexpr bool CW = true;                               \
-        constexpr int V = 1;                                    \
-        __VA_ARGS__;                                            \
-        break;                                                  \
-      }                                                         \
-    }                                                           \
-    if (lm) break;                                              \
-    constexpr bool CW = false;                                  \
-    if (vec2) {                                                 \
-      constexpr int V = 2;                                      \
-      __VA_ARGS__;                                              \
-    } else {                                                    \
-      constexpr int V = 1;                                      \
-      __VA_ARGS__;                                              \
-    }                                                           \
-  } while (0)
+hipError_t launch_qn_finalize(const Queue &q, const double *part, int nblocks, int nslots, double *res) {
+  hipLaunchKernelGGL(qn_finalize_kernel, dim3(nslots), dim3(BLOCK), 0, q.stream, part, nblocks, res);
+  return hipGetLastError();
+}
 
 template <typename T>
 hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
@@ -237,8 +169,7 @@ hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int c
   if (g == 0) return hipErrorInvalidValue;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(qn_finalize_kernel, dim3(2 * mc * k), dim3(BLOCK), 0, q.stream, (const double *)part, g, res);
-  return hipGetLastError();
+  return launch_qn_finalize(q, part, g, 2 * mc * k, res);
 }
 
 template <typename T>

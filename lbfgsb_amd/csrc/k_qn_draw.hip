@@ -1,0 +1,188 @@
+// k_qn_draw.hip -- draws x + sigma A^(1/2) z, z ~ N(0, I), of the curvature model (lbfgsb_hip_qn_draw, solver_qn.inl;
+// DESIGN.md section 10).  (part of the gfx950 kernel set; kernels_common.hpp has the overview)
+//
+// A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' (host_dense.hpp, qn_root).  The two passes are k_qn.hip's qn_wtv and
+// qn_expand with the loads of the vectors replaced by the generator: the Gaussian vectors never exist in memory.
+//   qn_wtz   [S'z_k; Y'z_k] for the K samples s0 .. s0 + K - 1 (every W entry read once per block of K samples);
+//   qn_draw  out_k = mean + (scale sqrt(alpha)) z_k + S cs_k + Y cy_k on the first column tile (z generated again),
+//            out_k += S cs_k + Y cy_k on the later ones (scale is folded into the coefficients by the host).
+// z_k[i] is a function of (seed, row0 + i, s0 + k) alone (philox.hpp): Philox4x32-10 on the counter (row, pair =
+// sample >> 1) under the key seed, Box-Muller on its two uniforms; the two samples of a pair share one Philox call
+// and one log / sqrt / sincospi.  A block of K >= 2 samples starts at an even sample (the host splits an odd first
+// sample off), so a block is K / 2 whole pairs.  REAL32: z and all arithmetic in fp64, rounded on store.
+// W is read as it lies (natural order or the tile-local layout through lmask); out and mean are in natural row order.
+#include "k_qn_common.hpp"
+#include "philox.hpp"
+
+namespace lbk {
+
+// z[kk] = the deviate of (seed, row, s0 + kk), kk < K.  K >= 2: s0 is even.
+template <int K>
+__device__ __forceinline__ void qn_gauss(uint64_t seed, uint64_t row, uint64_t s0, double (&z)[K]) {
+#pragma unroll
+  for (int pp = 0; pp < (K + 1) / 2; ++pp) {
+    double u, v, sn, cs;
+    lbp::uniforms(seed, row, (s0 >> 1) + (uint64_t)pp, u, v);
+    const double r = sqrt(-2.0 * log(u));
+    sincospi(2.0 * v, &sn, &cs);
+    if constexpr (K == 1) {
+      z[0] = (s0 & 1) ? r * sn : r * cs;
+    } else {
+      z[2 * pp] = r * cs;
+      z[2 * pp + 1] = r * sn;
+    }
+  }
+}
+
+// sums: slot kk * 2MC + j = S(:, c0 + j)' z_kk, slot kk * 2MC + MC + j = Y(:, c0 + j)' z_kk (qn_wtv_kernel's slots)
+template <typename T, int MC, int K, int V, bool CW, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_wtz_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                       int col, int c0, const uint64_t *__restrict__ lmask,
+                                                       uint64_t seed, int64_t row0, int64_t s0, double *part) {
+  static_assert(!CW || V == 1, "the layout is read one row per lane");
+  double acc[2 * MC * K];
+#pragma unroll
+  for (int k = 0; k < 2 * MC * K; ++k) acc[k] = 0.0;
+  for_rows<T, V>(n, [&](int64_t i, auto wt) {
+    constexpr int W = decltype(wt)::value;
+    const int64_t s = qn_slot<CW>(lmask, i);
+    double a[MC][W], b[MC][W];
+#pragma unroll
+    for (int j = 0; j < MC; ++j) {
+      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
+      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
+      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      double z[K];
+      qn_gauss<K>(seed, (uint64_t)(row0 + i + w), (uint64_t)s0, z);
+#pragma unroll
+      for (int kk = 0; kk < K; ++kk)
+#pragma unroll
+        for (int j = 0; j < MC; ++j) {
+          acc[kk * 2 * MC + j] += a[j][w] * z[kk];
+          acc[kk * 2 * MC + MC + j] += b[j][w] * z[kk];
+        }
+    }
+  });
+  block_reduce_store<2 * MC * K>(acc, 2 * MC * K, 0, 0, part, MAX_BLOCKS);
+}
+
+// first (tile c0 = 0): out_kk[i] =mean[i] + cf.alpha z_kk[i] + sum_j cf.c[kk][j] S(i, j) + cf.c[kk][MC + j] Y(i, j)
+// with mean[i] = 0 for a NULL mean; later tiles: out_kk[i] += sum_j ... over the columns c0 + j
+template <typename T, int MC, int K, int V, bool CW, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_draw_kernel(int64_t n, const T *__restrict__ ws,
+                                                        const T *__restrict__ wy, const T *__restrict__ zero,
+                                                        int64_t ldw, int m, int head, int col, int c0,
+                                                        const uint64_t *__restrict__ lmask, QnCoef<MC, K> cf,
+                                                        uint64_t seed, int64_t row0, int64_t s0, int first,
+                                                        const T *__restrict__ mean, QnOuts<T> out) {
+  static_assert(!CW || V == 1, "the layout is read one row per lane");
+  for_rows<T, V>(n, [&](int64_t i, auto wt) {
+    constexpr int W = decltype(wt)::value;
+    const int64_t s = qn_slot<CW>(lmask, i);
+    double x[K][W], a[MC][W], b[MC][W];
+#pragma unroll
+    for (int j = 0; j < MC; ++j) {
+      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
+      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
+      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
+    }
+    if (first) {
+      double mu[W];
+#pragma unroll
+      for (int w = 0; w < W; ++w) mu[w] = 0.0;
+      if (mean) ldx<W, false>(mean + i, mu);
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        double z[K];
+        qn_gauss<K>(seed, (uint64_t)(row0 + i + w), (uint64_t)s0, z);
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk) x[kk][w] = mu[w] + cf.alpha * z[kk];
+      }
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < K; ++kk) ldx<W, false>(out.p[kk] + i, x[kk]);
+    }
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) {
+      double o[W];
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        double e = x[kk][w];
+#pragma unroll
+        for (int j = 0; j < MC; ++j) {
+          e += cf.c[kk][j] * a[j][w];
+          e += cf.c[kk][MC + j] * b[j][w];
+        }
+        o[w] = e;
+      }
+      stnt<W>(out.p[kk] + i, o);
+    }
+  });
+}
+
+// ---------------------------------------------------------------- launches (dispatch: k_qn_common.hpp)
+namespace {
+// blocks of 1, 2 or 4 samples; a block of more than one sample is whole pairs
+bool draw_block_ok(int mc, int k, int64_t s0) {
+  return k >= 1 && k <= qn_kmax(mc) && k != 3 && s0 >= 0 && (k == 1 || (s0 & 1) == 0);
+}
+}  // namespace
+
+template <typename T>
+hipError_t launch_qn_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                         uint64_t seed, int64_t row0, int64_t s0, double *part, double *res) {
+  if (!draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
+  // (two rows per lane only where operands + accumulators leave room for them, as qn_wtv)
+  const bool vec2 = 2 * mc * k <= 20;
+  int g = 0;
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
+    auto kern = qn_wtz_kernel<T, MC, K, V, CW, NT>;
+    g = grid_for_w(q, n, V, (const void *)kern);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
+                       w.lmask, seed, row0, s0, part);
+  }))));
+  if (g == 0) return hipErrorInvalidValue;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_qn_finalize(q, part, g, 2 * mc * k, res);
+}
+
+template <typename T>
+hipError_t launch_qn_draw(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                          const double *coef, double alpha, uint64_t seed, int64_t row0, int64_t s0, bool first,
+                          const T *mean, QnOuts<T> out) {
+  if (!draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
+  // (out / mean that are not 16-byte aligned: one row per lane)
+  bool vec2 = 2 * mc * k <= 20 && (!mean || aligned_for(mean, 2));
+  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for((const T *)out.p[kk], 2);
+  bool done = false;
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
+    QnCoef<MC, K> cf{};
+    cf.alpha = alpha;
+    for (int kk = 0; kk < K; ++kk)
+      for (int j = 0; j < 2 * MC; ++j) cf.c[kk][j] = coef[(size_t)kk * 2 * MC + j];
+    auto kern = qn_draw_kernel<T, MC, K, V, CW, NT>;
+    const int g = grid_for_w(q, n, V, (const void *)kern);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
+                       w.lmask, cf, seed, row0, s0, first ? 1 : 0, first ? mean : (const T *)nullptr, out);
+    done = true;
+  }))));
+  if (!done) return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+#define QN_DRAW_INST(T)                                                                                           \
+  template hipError_t launch_qn_wtz<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, uint64_t,     \
+                                       int64_t, int64_t, double *, double *);                                    \
+  template hipError_t launch_qn_draw<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,              \
+                                        const double *, double, uint64_t, int64_t, int64_t, bool, const T *,    \
+                                        QnOuts<T>);
+QN_DRAW_INST(double)
+QN_DRAW_INST(float)
+#undef QN_DRAW_INST
+
+}  // namespace lbk

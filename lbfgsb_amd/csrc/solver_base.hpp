@@ -156,6 +156,9 @@ struct lbfgsb_hip_ctx {
   // the curvature model of the last return as a device operator (solver_qn.inl, lbfgsb_hip_qn_apply / qn_diag)
   virtual int qn_apply(int mode, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) = 0;
   virtual int qn_diag(int mode, void *out) = 0;
+  virtual int qn_logdet(int mode, double *h_logdet) = 0;
+  virtual int qn_draw(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean, double scale, void *out,
+                      int64_t ldo) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

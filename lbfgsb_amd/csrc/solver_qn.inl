@@ -1,6 +1,7 @@
 // solver_qn.inl -- member functions of Solver<T> (included inside the class body in solver.hip): the
 // limited-memory curvature model B and its inverse H = B^-1 as device operators (lbfgsb_hip_qn_apply,
-// lbfgsb_hip_qn_diag; k_qn.hip has the kernels, host_dense.hpp the 2col x 2col algebra).
+// lbfgsb_hip_qn_diag; k_qn.hip has the kernels, host_dense.hpp the 2col x 2col algebra), their
+// symmetric square roots, log-determinants and draws (lbfgsb_hip_qn_logdet, lbfgsb_hip_qn_draw; k_qn_draw.hip).
 //
 // The entries read the pairs of the last return (or import) and nothing else of the iteration's state changes:
 // W is read in the layout it is in (Wc(), never W()), the sums go through buffers of their own (never q.d_part /
@@ -17,6 +18,9 @@
     int64_t gram_gen = -1;      // generation of the Gram below
     std::vector<double> sty, yty;  // S'Y, Y'Y over all rows (col x col, logical order)
     int64_t n_gen[2] = {-1, -1};   // generation of the packed N of each mode (device copy in d_n[mode])
+    int64_t root_gen[2] = {-1, -1};  // generation of the root of each mode below (qn_root_coef)
+    std::vector<double> root_c[2];   // C of A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' (2col x 2col, column-major)
+    double root_logsum[2] = {0.0, 0.0};  // sum_i log1p(delta_i / alpha): log det A - n log alpha
     double *d_part = nullptr, *d_res = nullptr, *d_res_all = nullptr, *d_n[2] = {nullptr, nullptr};
     int all_ranks = 0;          // ranks d_res_all was sized for
     double *h_n = nullptr;      // pinned staging of a packed N
@@ -100,13 +104,33 @@
     if (e == hipSuccess) return 0;
     return fail(LBFGSB_E_NOGPU, std::string("qn: launch of ") + what + " failed: " + hipGetErrorString(e));
   }
+  struct QnPiece {  // one launch of a W'V pass: the vectors k0 .. k0 + k - 1 on the column tile at c0, sums at off
+    int c0, mc, k0, k, off;
+  };
   // [S'v_k; Y'v_k] for kc <= QN_KMAX vectors -> out[k * 2 col + i] (i < col: S, else Y), all ranks reduced
   int qn_sums(const T *const *v, int kc, bool vslot, double *out) {
-    const int col = qn.col;
     const lbk::WStore<T> w = Wc();
-    struct Piece {
-      int c0, mc, k0, k, off;
-    };
+    return qn_sums_by(kc, out, [&](const QnPiece &p) {
+      lbk::QnVecs<T> vv{};
+      for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
+      return qn_launched(lbk::launch_qn_wtv<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, vslot, qn.d_part,
+                                               qn.d_res + p.off),
+                         "qn_wtv");
+    });
+  }
+  // the same with the vectors generated: the samples s0 .. s0 + kc - 1 of seed (s0 even unless kc = 1)
+  int qn_sums_z(uint64_t seed, int64_t s0, int kc, double *out) {
+    const lbk::WStore<T> w = Wc();
+    return qn_sums_by(kc, out, [&](const QnPiece &p) {
+      return qn_launched(lbk::launch_qn_wtz<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, seed, row0, s0 + p.k0,
+                                               qn.d_part, qn.d_res + p.off),
+                         "qn_wtz");
+    });
+  }
+  template <typename L>
+  int qn_sums_by(int kc, double *out, L &&launch) {
+    const int col = qn.col;
+    using Piece = QnPiece;
     std::vector<Piece> pieces;
     int off = 0;
     for (int c0 = 0; c0 < col; c0 += lbk::QN_TILE) {
@@ -121,13 +145,7 @@
     }
     // (<= 2 (col + QN_TILE) kc <= QN_RES for every col <= LBFGSB_MAX_M; checked before anything is written)
     if (off > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");
-    for (const Piece &p : pieces) {
-      lbk::QnVecs<T> vv{};
-      for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
-      CHK(qn_launched(lbk::launch_qn_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, vslot, qn.d_part,
-                                            qn.d_res + p.off),
-                      "qn_wtv"));
-    }
+    for (const Piece &p : pieces) CHK(launch(p));
     CHK(qn_reduce(off));
     for (const Piece &p : pieces)
       for (int kk = 0; kk < p.k; ++kk)
@@ -176,12 +194,118 @@
     return info ? fail(LBFGSB_E_STATE, "qn: the middle matrix is singular (wt)") : 0;
   }
 
-  int qn_apply(int mode, int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) override {
+  // C of A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' and the log-det sum of B (inv = false) or H, once per pair
+  // generation (host_dense.hpp, qn_root): G = [S, Y]'[S, Y] from ss and the Gram, N as qn_diag forms it
+  int qn_root_coef(bool inv) {
+    const int col = qn.col, md = inv ? 1 : 0, d = 2 * col;
+    if (col > LBFGSB_QN_ROOT_MAXCOL) return fail(LBFGSB_E_ARG, "qn: a root of more than 64 stored pairs");
+    if (col == 0) return 0;
+    CHK(qn_gram());
+    if (qn.root_gen[md] == qn.gen) return 0;
+    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
+    const std::vector<double> dg = qn_dg();
+    std::vector<double> nm((size_t)d * d), g((size_t)d * d), work((size_t)6 * d * d + d);
+    const int info = lbh::qn_nmat(
+        col, [&](const double *stv, const double *ytv, double *cs, double *cy) {
+          return qn_coef(inv, dg.data(), stv, ytv, cs, cy);
+        },
+        nm.data());
+    if (info) return info;
+    for (int j = 0; j < col; ++j)
+      for (int i = 0; i < col; ++i) {
+        g[i + (size_t)j * d] = ss[(size_t)std::min(i, j) + (size_t)std::max(i, j) * m];
+        g[i + (size_t)(col + j) * d] = g[(col + j) + (size_t)i * d] = qn.sty[i + (size_t)j * col];
+        g[(col + i) + (size_t)(col + j) * d] = qn.yty[i + (size_t)j * col];
+      }
+    for (int j = 0; j < d; ++j)  // (Y'Y as the Gram pass summed it: symmetric up to rounding)
+      for (int i = 0; i < j; ++i) {
+        const double v = 0.5 * (g[i + (size_t)j * d] + g[j + (size_t)i * d]);
+        g[i + (size_t)j * d] = g[j + (size_t)i * d] = v;
+      }
+    qn.root_c[md].assign((size_t)d * d, 0.0);
+    qn.root_gen[md] = -1;
+    const int rc =
+        lbh::qn_root(d, alpha, g.data(), nm.data(), qn.root_c[md].data(), &qn.root_logsum[md], work.data());
+    if (rc == -2) return fail(LBFGSB_E_STATE, "qn: the model is not positive definite");
+    if (rc) return fail(LBFGSB_E_STATE, "qn: the eigensolver of the root did not converge");
+    qn.root_gen[md] = qn.gen;
+    return 0;
+  }
+  // c = f C sums for one vector (sums = [S'v; Y'v], 2col each)
+  void qn_root_map(bool inv, double f, const double *sums, double *c) const {
+    const int d = 2 * qn.col;
+    const double *cm = qn.root_c[inv ? 1 : 0].data();
+    for (int i = 0; i < d; ++i) {
+      double t = 0.0;
+      for (int j = 0; j < d; ++j) t = t + cm[i + (size_t)j * d] * sums[j];
+      c[i] = f * t;
+    }
+  }
+
+  int qn_logdet(int mode, double *h_logdet) override {
     CHK(qn_ready());
     const bool inv = mode == LBFGSB_QN_H;
-    const int col = qn.col;
-    if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
+    CHK(qn_root_coef(inv));
     const double alpha = inv ? 1.0 / qn.theta : qn.theta;
+    *h_logdet = (double)nglob * std::log(alpha) + (qn.col > 0 ? qn.root_logsum[inv ? 1 : 0] : 0.0);
+    return 0;
+  }
+
+  // out_j = mean + scale A^(1/2) z_(first + j): per block of samples the W'z sums, c = scale C sums on the host, then
+  // the expansion with z generated again (k_qn_draw.hip).  A block of more than one sample starts at an even sample.
+  int qn_draw(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean_, double scale, void *out_,
+              int64_t ldo) override {
+    CHK(qn_ready());
+    const bool inv = mode == LBFGSB_QN_H;
+    CHK(qn_root_coef(inv));
+    const int col = qn.col;
+    const double ra = std::sqrt(inv ? 1.0 / qn.theta : qn.theta);
+    const lbk::WStore<T> w = Wc();
+    const T *mean = (const T *)mean_;
+    T *out = (T *)out_;
+    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf(sums.size());
+    for (int64_t k0 = 0; k0 < k;) {
+      const int64_t s0 = first + k0;
+      const int kc = (s0 & 1) ? 1 : (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
+      if (col > 0) {
+        CHK(qn_sums_z(seed, s0, kc, sums.data()));
+        for (int kk = 0; kk < kc; ++kk)
+          qn_root_map(inv, scale, sums.data() + (size_t)kk * 2 * col, cf.data() + (size_t)kk * 2 * col);
+      }
+      for (int c0 = 0; c0 < std::max(col, 1); c0 += lbk::QN_TILE) {
+        const int mc = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col - c0)));
+        for (int j0 = 0; j0 < kc;) {
+          int kb = std::min(kc - j0, lbk::qn_kmax(mc));
+          if (kb == 3) kb = 2;
+          double coef[2 * lbk::QN_TILE * lbk::QN_KMAX] = {};
+          lbk::QnOuts<T> dst{};
+          for (int kk = 0; kk < kb; ++kk) {
+            const double *c = cf.data() + (size_t)(j0 + kk) * 2 * col;
+            for (int j = 0; j < mc && c0 + j < col; ++j) {
+              coef[(size_t)kk * 2 * mc + j] = c[c0 + j];
+              coef[(size_t)kk * 2 * mc + mc + j] = c[col + c0 + j];
+            }
+            dst.p[kk] = out + (k0 + j0 + kk) * ldo;
+          }
+          CHK(qn_launched(lbk::launch_qn_draw<T>(q, n, w, qn.head, col, c0, mc, kb, coef, scale * ra, seed, row0,
+                                                 s0 + j0, c0 == 0, mean, dst),
+                          "qn_draw"));
+          j0 += kb;
+        }
+      }
+      k0 += kc;
+    }
+    return qn_finish();
+  }
+
+  int qn_apply(int mode, int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) override {
+    CHK(qn_ready());
+    const bool inv = mode == LBFGSB_QN_H || mode == LBFGSB_QN_H_SQRT;
+    const bool root = mode == LBFGSB_QN_B_SQRT || mode == LBFGSB_QN_H_SQRT;
+    const int col = qn.col;
+    if (root) CHK(qn_root_coef(inv));
+    if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
+    const double alpha = root ? std::sqrt(inv ? 1.0 / qn.theta : qn.theta) : inv ? 1.0 / qn.theta : qn.theta;
     const std::vector<double> dg = qn_dg();
     const lbk::WStore<T> w = Wc();
     const T *v = (const T *)v_;
@@ -196,7 +320,8 @@
         for (int kk = 0; kk < kc; ++kk) {
           const double *sv = sums.data() + (size_t)kk * 2 * col;
           double *c = cf.data() + (size_t)kk * 2 * col;
-          CHK(qn_coef(inv, dg.data(), sv, sv + col, c, c + col));
+          if (root) qn_root_map(inv, 1.0, sv, c);
+          else CHK(qn_coef(inv, dg.data(), sv, sv + col, c, c + col));
         }
       }
       // out = alpha v + [S, Y] (cs; cy), one launch per column tile and block of vectors (col = 0: alpha v)

@@ -45,6 +45,8 @@
       public :: lbfgsb_qn_apply, lbfgsb_qn_diag        ! the curvature model B, H = B^-1 of the last return on the
                                                        ! device (lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag)
       integer,parameter,public :: LBFGSB_QN_B = 0, LBFGSB_QN_H = 1
+      integer,parameter,public :: LBFGSB_QN_B_SQRT = 4, LBFGSB_QN_H_SQRT = 5   ! lbfgsb_qn_apply only: A^(1/2) v
+      public :: lbfgsb_qn_logdet, lbfgsb_qn_draw       ! log det A and draws mean + scale A^(1/2) z, z ~ N(0, I)
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
                                                        ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
       ! slots of lbfgsb_kkt's cnt(:) and val(:): the header's LBFGSB_KKT_* indices + 1 (Fortran arrays start at 1)
@@ -155,6 +157,22 @@
             integer(c_int),value :: mode
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_diag
+         function lbfgsb_hip_qn_logdet(ctx,mode,logdet) bind(C,name='lbfgsb_hip_qn_logdet') result(rc)
+            import :: c_int, c_double, c_ptr
+            type(c_ptr),value :: ctx
+            integer(c_int),value :: mode
+            real(c_double) :: logdet
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_logdet
+         function lbfgsb_hip_qn_draw(ctx,mode,k,seed,first,mean,scale,out,ldo) bind(C,name='lbfgsb_hip_qn_draw') &
+            result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, mean, out
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, seed, first, ldo
+            real(c_double),value :: scale
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_draw
          function lbfgsb_hip_kkt(ctx,x,l,u,nbd,g,tol,pg,mult,status,cnt,val) bind(C,name='lbfgsb_hip_kkt') result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
             type(c_ptr),value :: ctx, x, l, u, nbd, g, pg, mult, status
@@ -427,6 +445,30 @@
       integer,intent(out) :: rc
       rc = lbfgsb_hip_qn_diag(ctx, int(mode, c_int), out)
       end subroutine lbfgsb_qn_diag
+
+      ! Square roots, log-determinants and draws of the model (include/lbfgsb_hip.h, same block).  lbfgsb_qn_apply
+      ! takes LBFGSB_QN_B_SQRT / LBFGSB_QN_H_SQRT for out_j = A^(1/2) v_j.  lbfgsb_qn_logdet: logdet = log det A over
+      ! the rows of all ranks (mode LBFGSB_QN_B or LBFGSB_QN_H).  lbfgsb_qn_draw: out_j = mean + scale A^(1/2)
+      ! z_(first + j), j < k, result j at out + j*ldo (device buffers of the context's real kind; mean may be
+      ! c_null_ptr); z is generated on the device from seed (an integer(c_int64_t) holding the 64-bit pattern), the
+      ! global row and the sample index alone.  At most 64 stored pairs.
+      subroutine lbfgsb_qn_logdet(ctx, mode, logdet, rc)
+      type(c_ptr),intent(in) :: ctx
+      integer,intent(in) :: mode
+      real(c_double),intent(out) :: logdet
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_logdet(ctx, int(mode, c_int), logdet)
+      end subroutine lbfgsb_qn_logdet
+
+      subroutine lbfgsb_qn_draw(ctx, mode, k, seed, first, mean, scale, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, mean, out
+      integer,intent(in) :: mode, k, first, ldo
+      integer(c_int64_t),intent(in) :: seed
+      real(c_double),intent(in) :: scale
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_draw(ctx, int(mode, c_int), int(k, c_int64_t), seed, int(first, c_int64_t), mean, scale, &
+                              out, int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_draw
 
       ! The active set, the multipliers and the projected gradient (include/lbfgsb_hip.h, "The active set, the bound
       ! multipliers and the projected gradient as device data"): one pass over the device arrays x, l, u, nbd, g of

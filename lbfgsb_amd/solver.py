@@ -345,10 +345,11 @@ class DeviceSolver:
         if self.same_stream_objective or self.stream_ordered:
             self.release_to_stream()  # (out is ordered on the solver's stream only: torch's stream waits for it)
 
-    def qn_apply(self, v, out=None, inverse: bool = False):
+    def qn_apply(self, v, out=None, inverse: bool = False, sqrt: bool = False):
         """out = B v (inverse=False) or H v = B^-1 v (inverse=True) for v of shape (n,) or (k, n): the limited-memory
         model of the last return (or import_state), theta I updated by the stored pairs -- H is exactly the inverse
-        of the matrix the solver uses (scipy's hess_inv starts from H0 = I instead).  Returns out."""
+        of the matrix the solver uses (scipy's hess_inv starts from H0 = I instead).  sqrt=True: the symmetric
+        square root B^(1/2) v or H^(1/2) v (at most 64 stored pairs).  Returns out."""
         v = self._qn_vec(v, "v")
         if out is None:
             import torch
@@ -360,8 +361,8 @@ class DeviceSolver:
         ldv = self.n if v.dim() == 1 else v.stride(0)
         ldo = self.n if out.dim() == 1 else out.stride(0)
         self.wait_stream()
-        check(self.lib.lbfgsb_hip_qn_apply(self.h, capi.QN_H if inverse else capi.QN_B, k, v.data_ptr(), ldv,
-                                           out.data_ptr(), ldo))
+        mode = (capi.QN_H_SQRT if inverse else capi.QN_B_SQRT) if sqrt else (capi.QN_H if inverse else capi.QN_B)
+        check(self.lib.lbfgsb_hip_qn_apply(self.h, mode, k, v.data_ptr(), ldv, out.data_ptr(), ldo))
         self._qn_done()
         return out
 
@@ -376,6 +377,40 @@ class DeviceSolver:
             raise ValueError("out must have shape (n,)")
         self.wait_stream()
         check(self.lib.lbfgsb_hip_qn_diag(self.h, capi.QN_H if inverse else capi.QN_B, out.data_ptr()))
+        self._qn_done()
+        return out
+
+    def qn_logdet(self, inverse: bool = False) -> float:
+        """log det B (inverse=False) or log det H = -log det B over all n_global rows, the same value on every rank
+        (collective on sharded contexts; at most 64 stored pairs)."""
+        val = C.c_double(0.0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_logdet(self.h, capi.QN_H if inverse else capi.QN_B, C.byref(val)))
+        return val.value
+
+    def qn_draw(self, k: int, seed: int, first: int = 0, mean=None, scale: float = 1.0, inverse: bool = True,
+                out=None):
+        """k draws from N(mean, scale^2 A), A = H (inverse=True) or B, as a (k, n) tensor: row j is mean + scale
+        A^(1/2) z_(first + j).  The standard normal z_s is generated on the device inside the passes over W; its
+        entry for a row depends on (seed, the global row, s) alone -- not on the sharding or on k.  seed: any
+        integer below 2^64.  mean: an (n,) tensor or None.  Returns out."""
+        import torch
+        dt = torch.float32 if self.real == np.float32 else torch.float64
+        if out is None:
+            out = torch.empty((int(k), self.n), dtype=dt, device=torch.device("cuda", self.device))
+        out = self._qn_vec(out, "out")
+        if (out.dim() == 1 and k != 1) or (out.dim() == 2 and out.shape[0] != k):
+            raise ValueError("out must have shape (k, n)")
+        if mean is not None:
+            mean = self._qn_vec(mean, "mean")
+            if mean.dim() != 1:
+                raise ValueError("mean must have shape (n,)")
+        ldo = self.n if out.dim() == 1 else out.stride(0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_draw(self.h, capi.QN_H if inverse else capi.QN_B, int(k),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
+                                          None if mean is None else mean.data_ptr(), float(scale), out.data_ptr(),
+                                          ldo))
         self._qn_done()
         return out
 
@@ -691,21 +726,40 @@ class QnOperator:
     op @ v and op.matvec(v) take an (n,) tensor, op.matmat(V) an (n, k) one (columns are vectors, as in scipy);
     op.diagonal() is diag(A).  Every call reads the solver's state as it is at that moment."""
 
-    def __init__(self, solver: DeviceSolver, inverse: bool = True):
-        self.solver, self.inverse = solver, bool(inverse)
+    def __init__(self, solver: DeviceSolver, inverse: bool = True, root: bool = False):
+        self.solver, self.inverse, self.root = solver, bool(inverse), bool(root)
         self.shape = (solver.n, solver.n)
         self.dtype = np.dtype(solver.real)
 
     def matvec(self, v):
-        return self.solver.qn_apply(v, inverse=self.inverse)
+        return self.solver.qn_apply(v, inverse=self.inverse, sqrt=self.root)
 
     def matmat(self, vs):
         if vs.dim() != 2 or vs.shape[0] != self.shape[1]:
             raise ValueError("matmat takes an (n, k) tensor")
-        return self.solver.qn_apply(vs.t().contiguous(), inverse=self.inverse).t()
+        return self.solver.qn_apply(vs.t().contiguous(), inverse=self.inverse, sqrt=self.root).t()
 
     def diagonal(self):
+        if self.root:
+            raise ValueError("qn_diag takes B or H, not a square root")
         return self.solver.qn_diag(inverse=self.inverse)
+
+    def sqrt(self) -> "QnOperator":
+        """the symmetric square root A^(1/2) of this operator, with matvec / matmat (at most 64 stored pairs)"""
+        if self.root:
+            raise ValueError("this operator is a square root already")
+        return QnOperator(self.solver, self.inverse, root=True)
+
+    def logdet(self) -> float:
+        """log det A over all rows of all ranks (of a root: half of it)"""
+        v = self.solver.qn_logdet(inverse=self.inverse)
+        return 0.5 * v if self.root else v
+
+    def sample(self, k: int, seed: int, first: int = 0, mean=None, scale: float = 1.0):
+        """k draws from N(mean, scale^2 A) as a (k, n) tensor (DeviceSolver.qn_draw)"""
+        if self.root:
+            raise ValueError("sample() draws with covariance A: call it on the operator, not on its root")
+        return self.solver.qn_draw(k, seed, first=first, mean=mean, scale=scale, inverse=self.inverse)
 
     def __matmul__(self, v):
         return self.matvec(v) if v.dim() == 1 else self.matmat(v)
