@@ -406,6 +406,27 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  *     r cospi(2v), an odd one r sinpi(2v).  REAL32 contexts: z and all arithmetic in fp64, rounded on store.
  * When, streams and refusals are qn_apply's.  LBFGSB_E_ARG in addition: NULL out / h_logdet, k < 1, first < 0,
  * ldo < n_local, a mode other than B / H, a scale that is not finite.
+ *
+ * Quadratic forms and Gaussian log-densities.  With d = v - center and p = [S, Y]'d, d'A d = alpha d'd + p'N p: ONE
+ * pass over W per block of 4 vectors, which carries d'd along and writes nothing.  All results are host doubles,
+ * complete over all ranks and the same bits on each; the entries wait for their sums whatever
+ * LBFGSB_F_NO_RETURN_SYNC says, as lbfgsb_hip_kkt's summary does.
+ *   qn_quad: h_q[j] = (v_j - center)' A (v_j - center) over all n_global rows, j < k, vector j at v + j*ldv.  mode is
+ *     LBFGSB_QN_B or LBFGSB_QN_H and names A; the root modes and the modes 2 and 3 are LBFGSB_E_ARG (the quadratic
+ *     form of A^(1/2) is not offered).  center (n_local reals) may be NULL; it is read once per vector.  Any number
+ *     of stored pairs.  REAL32 contexts: v and center are fp32, the difference and every sum fp64.
+ *   qn_logpdf: h_logp[j] = -1/2 [ n_global log 2 pi + 2 n_global log |scale| + log det A + q_j / scale^2 ], the
+ *     log-density of N(mean, scale^2 A) at x_j.  mode names the COVARIANCE A, as it does for qn_draw; q_j is the
+ *     quadratic form of the OTHER mode (A^-1) at x_j - mean.  log det A is qn_logdet's: the same cache, at most
+ *     LBFGSB_QN_ROOT_MAXCOL stored pairs, LBFGSB_E_STATE for a model that is not positive definite.
+ *   qn_draw_logpdf: qn_draw -- out is bit for bit what qn_draw writes for the same arguments -- which also returns
+ *     h_logp[j] = -1/2 [ n_global log 2 pi + 2 n_global log |scale| + log det A + z_(first + j)' z_(first + j) ],
+ *     the log-density of draw j under N(mean, scale^2 A), with z the generated fp64 deviates: z'z is summed inside
+ *     the W'z pass, where every z already is in a register.  REAL32 contexts: this is the density of the draw
+ *     BEFORE it is rounded to fp32 on store; qn_logpdf at the stored fp32 draw differs by that rounding.
+ * When, streams, the collective rule and the refusals are qn_apply's.  LBFGSB_E_ARG in addition, changing nothing:
+ * NULL v / x / out / h_q / h_logp, k < 1, first < 0, ld < n_local, a mode other than B / H, and for the two
+ * log-densities a scale that is 0 or not finite.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
@@ -419,6 +440,12 @@ int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out);
 int lbfgsb_hip_qn_logdet(lbfgsb_hip_ctx *ctx, int mode, double *h_logdet);
 int lbfgsb_hip_qn_draw(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first, const void *mean,
                        double scale, void *out, int64_t ldo);
+int lbfgsb_hip_qn_quad(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, const void *center,
+                       double *h_q);
+int lbfgsb_hip_qn_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *x, int64_t ldx, const void *mean,
+                         double scale, double *h_logp);
+int lbfgsb_hip_qn_draw_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first,
+                              const void *mean, double scale, void *out, int64_t ldo, double *h_logp);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.

@@ -252,6 +252,31 @@ int lbfgsb_hip_qn_draw(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, 
   if (!std::isfinite(scale)) return fail(LBFGSB_E_ARG, "qn_draw: scale is not finite");
   return ctx->qn_draw(mode, k, seed, first, mean, scale, out, ldo);
 }
+int lbfgsb_hip_qn_quad(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, const void *center,
+                       double *h_q) {
+  if (!ctx || !v || !h_q) return fail(LBFGSB_E_ARG, "qn_quad: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_quad: mode");
+  if (k < 1 || ldv < ctx->n) return fail(LBFGSB_E_ARG, "qn_quad: k < 1 or ldv < n_local");
+  return ctx->qn_quad(mode, k, v, ldv, center, h_q);
+}
+int lbfgsb_hip_qn_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *x, int64_t ldx, const void *mean,
+                         double scale, double *h_logp) {
+  if (!ctx || !x || !h_logp) return fail(LBFGSB_E_ARG, "qn_logpdf: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_logpdf: mode");
+  if (k < 1 || ldx < ctx->n) return fail(LBFGSB_E_ARG, "qn_logpdf: k < 1 or ldx < n_local");
+  if (!std::isfinite(scale) || scale == 0.0) return fail(LBFGSB_E_ARG, "qn_logpdf: scale is 0 or not finite");
+  return ctx->qn_logpdf(mode, k, x, ldx, mean, scale, h_logp);
+}
+int lbfgsb_hip_qn_draw_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first,
+                              const void *mean, double scale, void *out, int64_t ldo, double *h_logp) {
+  if (!ctx || !out || !h_logp) return fail(LBFGSB_E_ARG, "qn_draw_logpdf: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_draw_logpdf: mode");
+  if (k < 1 || first < 0 || ldo < ctx->n)
+    return fail(LBFGSB_E_ARG, "qn_draw_logpdf: k < 1, first < 0 or ldo < n_local");
+  if (!std::isfinite(scale) || scale == 0.0)
+    return fail(LBFGSB_E_ARG, "qn_draw_logpdf: scale is 0 or not finite");
+  return ctx->qn_draw_logpdf(mode, k, seed, first, mean, scale, out, ldo, h_logp);
+}
 
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
                    const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,

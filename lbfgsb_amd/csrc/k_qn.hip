@@ -2,8 +2,9 @@
 // solver_qn.inl).  (part of the gfx950 kernel set; kernels_common.hpp has the overview)
 //
 // B = theta I + [S, Y] N_B [S, Y]'   and   H = B^-1 = theta^-1 I + [S, Y] N_H [S, Y]'
-// with the 2col x 2col matrices N formed on the host (host_dense.hpp, qn_coef_b / qn_coef_h).  Three passes:
+// with the 2col x 2col matrices N formed on the host (host_dense.hpp, qn_coef_b / qn_coef_h).  The passes:
 //   qn_wtv     [S'v; Y'v] for K vectors at once (every W entry read once per block of K vectors);
+//   qn_wtd     the same for d = v - center with d'd carried along: the one pass of a quadratic form d'A d;
 //   qn_expand  out_j = alpha src_j + S cs_j + Y cy_j (coefficients as kernel arguments);
 //   qn_diag    out_i = alpha + r_i' N r_i,  r_i = row i of [S, Y], N in LDS (upper triangle, off-diagonal doubled).
 // None of them writes W: they read it in the layout it is in (natural order, or the tile-local layout of k_layout.hip
@@ -17,26 +18,42 @@ namespace lbk {
 
 // sums: slot kk * 2MC + j = S(:, c0 + j)' v_kk, slot kk * 2MC + MC + j = Y(:, c0 + j)' v_kk (j >= col - c0: zero).
 // VSLOT: vector row i is read at the SLOT of row i (the vectors are columns of W themselves: the Gram).
-template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_wtv_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                       int col, int c0, const uint64_t *__restrict__ lmask,
-                                                       QnVecs<T> v, double *part) {
+// CEN: the vectors are d_kk = v_kk - center, formed in fp64 in registers (no center: neither a load nor an address).
+// DD: K more sums d_kk'd_kk in the slots 2MC K + kk (the first column tile's launch of a quadratic form carries them).
+// The plain pass (qn_wtv_kernel) is the body with both off.
+template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT, bool CEN, bool DD>
+__device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                            const T *__restrict__ zero, int64_t ldw, int m, int head, int col, int c0,
+                                            const uint64_t *__restrict__ lmask, const QnVecs<T> &v,
+                                            const T *__restrict__ center, double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
-  double acc[2 * MC * K];
+  static_assert(!VSLOT || !(CEN || DD), "a center and the squared norm belong to vectors in natural order");
+  constexpr int NW = 2 * MC * K, NACC = NW + (DD ? K : 0);
+  double acc[NACC];
 #pragma unroll
-  for (int k = 0; k < 2 * MC * K; ++k) acc[k] = 0.0;
+  for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
   for_rows<T, V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
     const int64_t s = qn_slot<CW>(lmask, i);
     double vv[K][W], a[MC][W], b[MC][W];
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) ldx<W, NT>(v.p[kk] + (VSLOT ? s : i), vv[kk]);
+    double cc[CEN ? W : 1];
+    if constexpr (CEN) ldx<W, NT>(center + i, cc);
 #pragma unroll
     for (int j = 0; j < MC; ++j) {
       const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
       ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
       ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
+    }
+    // (the differences after every load of the trip is issued, behind a fence for the scheduler: left free, it puts
+    //  them between the loads and waits for every column on its own in the natural-order K = 4 kernel)
+    if constexpr (CEN) {
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kk = 0; kk < K; ++kk)
+#pragma unroll
+        for (int w = 0; w < W; ++w) vv[kk][w] -= cc[w];
     }
 #pragma unroll
     for (int kk = 0; kk < K; ++kk)
@@ -47,8 +64,32 @@ __global__ __launch_bounds__(BLOCK) void qn_wtv_kernel(int64_t n, const T *__res
           acc[kk * 2 * MC + j] += a[j][w] * vv[kk][w];
           acc[kk * 2 * MC + MC + j] += b[j][w] * vv[kk][w];
         }
+    if constexpr (DD) {
+#pragma unroll
+      for (int kk = 0; kk < K; ++kk)
+#pragma unroll
+        for (int w = 0; w < W; ++w) acc[NW + kk] += vv[kk][w] * vv[kk][w];
+    }
   });
-  block_reduce_store<2 * MC * K>(acc, 2 * MC * K, 0, 0, part, MAX_BLOCKS);
+  block_reduce_store<NACC>(acc, NACC, 0, 0, part, MAX_BLOCKS);
+}
+
+template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_wtv_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                       int col, int c0, const uint64_t *__restrict__ lmask,
+                                                       QnVecs<T> v, double *part) {
+  qn_wtv_body<T, MC, K, V, CW, VSLOT, NT, false, false>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, nullptr,
+                                                        part);
+}
+
+// the W'V pass of a quadratic form (lbfgsb_hip_qn_quad / qn_logpdf): the vectors centred, d'd on the first tile
+template <typename T, int MC, int K, int V, bool CW, bool NT, bool CEN, bool DD>
+__global__ __launch_bounds__(BLOCK) void qn_wtd_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                       int col, int c0, const uint64_t *__restrict__ lmask,
+                                                       QnVecs<T> v, const T *__restrict__ center, double *part) {
+  qn_wtv_body<T, MC, K, V, CW, false, NT, CEN, DD>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, center, part);
 }
 
 // res[k] = sum over the workgroups' partials of slot k, in a fixed order (one workgroup per slot)
@@ -173,6 +214,32 @@ hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int c
 }
 
 template <typename T>
+hipError_t launch_qn_wtd(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                         QnVecs<T> v, const T *center, bool dd, double *part, double *res) {
+  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
+  // (no center and no squared norm -- the later column tiles of an uncentred form: the plain pass itself)
+  if (!center && !dd) return launch_qn_wtv<T>(q, n, w, head, col, c0, mc, k, v, false, part, res);
+  // (rows per lane as qn_wtv: at the two-row shapes the K squared norms and the center's V entries add 2 (K + V) <= 8
+  //  registers to its operands and sums -- 140 against 136 at the largest, mc = 10, k = 1: three waves per SIMD still)
+  bool vec2 = 2 * mc * k <= 20 && (!center || aligned_for(center, 2));
+  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
+  int g = 0;
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT,
+      QN_DISPATCH_BOOL(center != nullptr, CEN, QN_DISPATCH_BOOL(dd, DD, {
+    if constexpr (CEN || DD) {
+      auto kern = qn_wtd_kernel<T, MC, K, V, CW, NT, CEN, DD>;
+      g = grid_for_w(q, n, V, (const void *)kern);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
+                         w.lmask, v, center, part);
+    }
+  }))))));
+  if (g == 0) return hipErrorInvalidValue;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_qn_finalize(q, part, g, 2 * mc * k + (dd ? k : 0), res);
+}
+
+template <typename T>
 hipError_t launch_qn_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                             const double *coef, double alpha, QnVecs<T> src, QnOuts<T> out) {
   if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
@@ -215,6 +282,8 @@ hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int 
 #define QN_INST(T)                                                                                                  \
   template hipError_t launch_qn_wtv<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
                                        bool, double *, double *);                                                 \
+  template hipError_t launch_qn_wtd<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
+                                       const T *, bool, double *, double *);                                      \
   template hipError_t launch_qn_expand<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,          \
                                           const double *, double, QnVecs<T>, QnOuts<T>);                         \
   template hipError_t launch_qn_diag<T>(const Queue &, int64_t, WStore<T>, int, int, const double *, double, T *);

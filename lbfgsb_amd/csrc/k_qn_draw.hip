@@ -4,6 +4,7 @@
 // A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' (host_dense.hpp, qn_root).  The two passes are k_qn.hip's qn_wtv and
 // qn_expand with the loads of the vectors replaced by the generator: the Gaussian vectors never exist in memory.
 //   qn_wtz   [S'z_k; Y'z_k] for the K samples s0 .. s0 + K - 1 (every W entry read once per block of K samples);
+//   qn_wtzz  the same with z_k'z_k carried along (the log-density of a draw, lbfgsb_hip_qn_draw_logpdf);
 //   qn_draw  out_k = mean + (scale sqrt(alpha)) z_k + S cs_k + Y cy_k on the first column tile (z generated again),
 //            out_k += S cs_k + Y cy_k on the later ones (scale is folded into the coefficients by the host).
 // z_k[i] is a function of (seed, row0 + i, s0 + k) alone (philox.hpp): Philox4x32-10 on the counter (row, pair =
@@ -35,15 +36,22 @@ __device__ __forceinline__ void qn_gauss(uint64_t seed, uint64_t row, uint64_t s
 }
 
 // sums: slot kk * 2MC + j = S(:, c0 + j)' z_kk, slot kk * 2MC + MC + j = Y(:, c0 + j)' z_kk (qn_wtv_kernel's slots)
-template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_wtz_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                       int col, int c0, const uint64_t *__restrict__ lmask,
-                                                       uint64_t seed, int64_t row0, int64_t s0, double *part) {
+// ZZ: K more sums z_kk'z_kk in the slots 2MC K + kk (lbfgsb_hip_qn_draw_logpdf, the first column tile's launch).  The
+// W'z sums are the plain pass's bit for bit: the same rows per lane, the same operations on every accumulator and
+// the same reduction of every slot (block_reduce_store's order within a slot does not depend on the slot count,
+// and 2MC K and 2MC K + K are on the same side of its scatter threshold for every MC, K here), on the same grid
+// (launch_qn_wtz sizes it from the plain kernel for both).
+template <typename T, int MC, int K, int V, bool CW, bool NT, bool ZZ>
+__device__ __forceinline__ void qn_wtz_body(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                            const T *__restrict__ zero, int64_t ldw, int m, int head, int col, int c0,
+                                            const uint64_t *__restrict__ lmask, uint64_t seed, int64_t row0,
+                                            int64_t s0, double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
-  double acc[2 * MC * K];
+  constexpr int NW = 2 * MC * K, NACC = NW + (ZZ ? K : 0);
+  static_assert((NW >= 16) == (NACC >= 16), "block_reduce_store reduces the W'z slots as the plain pass does");
+  double acc[NACC];
 #pragma unroll
-  for (int k = 0; k < 2 * MC * K; ++k) acc[k] = 0.0;
+  for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
   for_rows<T, V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
     const int64_t s = qn_slot<CW>(lmask, i);
@@ -65,9 +73,29 @@ __global__ __launch_bounds__(BLOCK) void qn_wtz_kernel(int64_t n, const T *__res
           acc[kk * 2 * MC + j] += a[j][w] * z[kk];
           acc[kk * 2 * MC + MC + j] += b[j][w] * z[kk];
         }
+      if constexpr (ZZ) {
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk) acc[NW + kk] += z[kk] * z[kk];
+      }
     }
   });
-  block_reduce_store<2 * MC * K>(acc, 2 * MC * K, 0, 0, part, MAX_BLOCKS);
+  block_reduce_store<NACC>(acc, NACC, 0, 0, part, MAX_BLOCKS);
+}
+
+template <typename T, int MC, int K, int V, bool CW, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_wtz_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                       int col, int c0, const uint64_t *__restrict__ lmask,
+                                                       uint64_t seed, int64_t row0, int64_t s0, double *part) {
+  qn_wtz_body<T, MC, K, V, CW, NT, false>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, seed, row0, s0, part);
+}
+
+template <typename T, int MC, int K, int V, bool CW, bool NT>
+__global__ __launch_bounds__(BLOCK) void qn_wtzz_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                        const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                        int col, int c0, const uint64_t *__restrict__ lmask,
+                                                        uint64_t seed, int64_t row0, int64_t s0, double *part) {
+  qn_wtz_body<T, MC, K, V, CW, NT, true>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, seed, row0, s0, part);
 }
 
 // first (tile c0 = 0): out_kk[i] =mean[i] + cf.alpha z_kk[i] + sum_j cf.c[kk][j] S(i, j) + cf.c[kk][MC + j] Y(i, j)
@@ -134,21 +162,24 @@ bool draw_block_ok(int mc, int k, int64_t s0) {
 
 template <typename T>
 hipError_t launch_qn_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         uint64_t seed, int64_t row0, int64_t s0, double *part, double *res) {
+                         uint64_t seed, int64_t row0, int64_t s0, bool zz, double *part, double *res) {
   if (!draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
-  // (two rows per lane only where operands + accumulators leave room for them, as qn_wtv)
+  // (two rows per lane only where operands + accumulators leave room for them, as qn_wtv; the same with z'z, whose
+  //  K sums add 2 K <= 4 registers there: the W'z sums of the two kernels must agree bit for bit)
   const bool vec2 = 2 * mc * k <= 20;
   int g = 0;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
-    auto kern = qn_wtz_kernel<T, MC, K, V, CW, NT>;
-    g = grid_for_w(q, n, V, (const void *)kern);
+    auto kern = zz ? qn_wtzz_kernel<T, MC, K, V, CW, NT> : qn_wtz_kernel<T, MC, K, V, CW, NT>;
+    // (the grid of the PLAIN kernel for both: the grid decides every workgroup's rows, hence the partial sums, and
+    //  the two code objects need not be resident in the same numbers)
+    g = grid_for_w(q, n, V, (const void *)qn_wtz_kernel<T, MC, K, V, CW, NT>);
     hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
                        w.lmask, seed, row0, s0, part);
   }))));
   if (g == 0) return hipErrorInvalidValue;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return launch_qn_finalize(q, part, g, 2 * mc * k, res);
+  return launch_qn_finalize(q, part, g, 2 * mc * k + (zz ? k : 0), res);
 }
 
 template <typename T>
@@ -177,7 +208,7 @@ hipError_t launch_qn_draw(const Queue &q, int64_t n, WStore<T> w, int head, int 
 
 #define QN_DRAW_INST(T)                                                                                           \
   template hipError_t launch_qn_wtz<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, uint64_t,     \
-                                       int64_t, int64_t, double *, double *);                                    \
+                                       int64_t, int64_t, bool, double *, double *);                              \
   template hipError_t launch_qn_draw<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,              \
                                         const double *, double, uint64_t, int64_t, int64_t, bool, const T *,    \
                                         QnOuts<T>);

@@ -532,6 +532,11 @@ struct QnCoef {  // out_k = alpha src_k + S c[k][0..MC) + Y c[k][MC..2MC): <= 4 
 template <typename T>
 hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                          QnVecs<T> v, bool vslot, double *part, double *res);
+// The same for d_k = v_k - center (center may be NULL: the vectors as they are), vectors in natural order; dd: k more
+// sums d_k'd_k in res[2 mc k + kk] -- the W'V pass of a quadratic form, whose first tile carries the squared norms
+template <typename T>
+hipError_t launch_qn_wtd(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                         QnVecs<T> v, const T *center, bool dd, double *part, double *res);
 // res[k] = the sum of slot k's nblocks partials, k < nslots, in a fixed order (launch_qn_wtv / launch_qn_wtz end so)
 hipError_t launch_qn_finalize(const Queue &q, const double *part, int nblocks, int nslots, double *res);
 // out_k = alpha src_k + [S, Y](:, tile) coef[k * 2 mc ...] (src_k may be out_k: the second and later tiles)
@@ -546,10 +551,11 @@ hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int 
 // Draws of the model (k_qn_draw.hip): the two passes above with the vectors generated, never loaded -- z_k[i] is the
 // N(0, 1) deviate of (seed, row0 + i, s0 + k) (philox.hpp).  k = 1, 2 or 4 (qn_kmax) samples from s0; s0 even
 // unless k = 1.
-// [S'z_k; Y'z_k] of the tile's columns, as launch_qn_wtv lays them out
+// [S'z_k; Y'z_k] of the tile's columns, as launch_qn_wtv lays them out; zz: k more sums z_k'z_k in res[2 mc k + kk],
+// the other sums bit for bit what zz = false gives
 template <typename T>
 hipError_t launch_qn_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         uint64_t seed, int64_t row0, int64_t s0, double *part, double *res);
+                         uint64_t seed, int64_t row0, int64_t s0, bool zz, double *part, double *res);
 // first: out_k = mean + alpha z_k + [S, Y](:, tile) coef[k * 2 mc ...] (mean may be NULL); else out_k += [S, Y] coef
 template <typename T>
 hipError_t launch_qn_draw(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,

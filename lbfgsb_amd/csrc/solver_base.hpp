@@ -159,6 +159,11 @@ struct lbfgsb_hip_ctx {
   virtual int qn_logdet(int mode, double *h_logdet) = 0;
   virtual int qn_draw(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean, double scale, void *out,
                       int64_t ldo) = 0;
+  virtual int qn_quad(int mode, int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) = 0;
+  virtual int qn_logpdf(int mode, int64_t k, const void *x, int64_t ldx, const void *mean, double scale,
+                        double *h_logp) = 0;
+  virtual int qn_draw_logpdf(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean, double scale,
+                             void *out, int64_t ldo, double *h_logp) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

@@ -1,7 +1,8 @@
 // solver_qn.inl -- member functions of Solver<T> (included inside the class body in solver.hip): the
 // limited-memory curvature model B and its inverse H = B^-1 as device operators (lbfgsb_hip_qn_apply,
 // lbfgsb_hip_qn_diag; k_qn.hip has the kernels, host_dense.hpp the 2col x 2col algebra), their
-// symmetric square roots, log-determinants and draws (lbfgsb_hip_qn_logdet, lbfgsb_hip_qn_draw; k_qn_draw.hip).
+// symmetric square roots, log-determinants and draws (lbfgsb_hip_qn_logdet, lbfgsb_hip_qn_draw; k_qn_draw.hip), and
+// quadratic forms and Gaussian log-densities (lbfgsb_hip_qn_quad, qn_logpdf, qn_draw_logpdf).
 //
 // The entries read the pairs of the last return (or import) and nothing else of the iteration's state changes:
 // W is read in the layout it is in (Wc(), never W()), the sums go through buffers of their own (never q.d_part /
@@ -26,7 +27,8 @@
     double *h_n = nullptr;      // pinned staging of a packed N
     std::vector<double> h_res, h_all;
   } qn;
-  static constexpr int QN_RES = 2 * (LBFGSB_MAX_M + lbk::QN_TILE) * lbk::QN_KMAX;  // sums of one vector block
+  // sums of one vector block: 2 (col + QN_TILE) per vector, and its squared norm (quadratic forms, draw densities)
+  static constexpr int QN_RES = (2 * (LBFGSB_MAX_M + lbk::QN_TILE) + 1) * lbk::QN_KMAX;
   static constexpr int QN_NP = 64 * 65 / 2;                                         // packed N at 32 pairs
 
   // save_locals: what the entries will read until the next return
@@ -106,11 +108,12 @@
   }
   struct QnPiece {  // one launch of a W'V pass: the vectors k0 .. k0 + k - 1 on the column tile at c0, sums at off
     int c0, mc, k0, k, off;
+    bool sq;  // the launch carries the k squared norms too, behind its 2 mc k sums (the first tile, when asked for)
   };
   // [S'v_k; Y'v_k] for kc <= QN_KMAX vectors -> out[k * 2 col + i] (i < col: S, else Y), all ranks reduced
   int qn_sums(const T *const *v, int kc, bool vslot, double *out) {
     const lbk::WStore<T> w = Wc();
-    return qn_sums_by(kc, out, [&](const QnPiece &p) {
+    return qn_sums_by(kc, out, nullptr, [&](const QnPiece &p) {
       lbk::QnVecs<T> vv{};
       for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
       return qn_launched(lbk::launch_qn_wtv<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, vslot, qn.d_part,
@@ -119,41 +122,58 @@
     });
   }
   // the same with the vectors generated: the samples s0 .. s0 + kc - 1 of seed (s0 even unless kc = 1)
-  int qn_sums_z(uint64_t seed, int64_t s0, int kc, double *out) {
+  // zz (kc values, or NULL): z_k'z_k over all rows as well -- the other sums are the same bits either way
+  int qn_sums_z(uint64_t seed, int64_t s0, int kc, double *out, double *zz = nullptr) {
     const lbk::WStore<T> w = Wc();
-    return qn_sums_by(kc, out, [&](const QnPiece &p) {
+    return qn_sums_by(kc, out, zz, [&](const QnPiece &p) {
       return qn_launched(lbk::launch_qn_wtz<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, seed, row0, s0 + p.k0,
-                                               qn.d_part, qn.d_res + p.off),
+                                               p.sq, qn.d_part, qn.d_res + p.off),
                          "qn_wtz");
     });
   }
+  // the sums of d_k = v_k - center (center may be NULL) and dd[k] = d_k'd_k
+  int qn_sums_d(const T *const *v, int kc, const T *center, double *out, double *dd) {
+    const lbk::WStore<T> w = Wc();
+    return qn_sums_by(kc, out, dd, [&](const QnPiece &p) {
+      lbk::QnVecs<T> vv{};
+      for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
+      return qn_launched(lbk::launch_qn_wtd<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, center, p.sq,
+                                               qn.d_part, qn.d_res + p.off),
+                         "qn_wtd");
+    });
+  }
+  // sq (kc values) or NULL: the vectors' squared norms, carried by the launches of the first column tile -- with no
+  // stored pair by launches on an empty tile, which read the zero line and nothing of W
   template <typename L>
-  int qn_sums_by(int kc, double *out, L &&launch) {
+  int qn_sums_by(int kc, double *out, double *sq, L &&launch) {
     const int col = qn.col;
     using Piece = QnPiece;
     std::vector<Piece> pieces;
     int off = 0;
-    for (int c0 = 0; c0 < col; c0 += lbk::QN_TILE) {
-      const int mc = lbk::qn_mc(std::min(lbk::QN_TILE, col - c0));
+    for (int c0 = 0; c0 < std::max(col, sq ? 1 : 0); c0 += lbk::QN_TILE) {
+      const int mc = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col - c0)));
       for (int k0 = 0; k0 < kc;) {  // blocks of 4 / 2 / 1 vectors the tile's kernels take
         int k = std::min(kc - k0, lbk::qn_kmax(mc));
         if (k == 3) k = 2;
-        pieces.push_back(Piece{c0, mc, k0, k, off});
-        off += 2 * mc * k;
+        const bool carry = sq && c0 == 0;
+        pieces.push_back(Piece{c0, mc, k0, k, off, carry});
+        off += 2 * mc * k + (carry ? k : 0);
         k0 += k;
       }
     }
-    // (<= 2 (col + QN_TILE) kc <= QN_RES for every col <= LBFGSB_MAX_M; checked before anything is written)
+    // (<= (2 (col + QN_TILE) + 1) kc <= QN_RES for every col <= LBFGSB_MAX_M; checked before anything is written)
     if (off > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");
     for (const Piece &p : pieces) CHK(launch(p));
     CHK(qn_reduce(off));
     for (const Piece &p : pieces)
-      for (int kk = 0; kk < p.k; ++kk)
+      for (int kk = 0; kk < p.k; ++kk) {
         for (int j = 0; j < p.mc && p.c0 + j < col; ++j) {
           double *o = out + (size_t)(p.k0 + kk) * 2 * col;
           o[p.c0 + j] = qn.h_res[(size_t)p.off + kk * 2 * p.mc + j];
           o[col + p.c0 + j] = qn.h_res[(size_t)p.off + kk * 2 * p.mc + p.mc + j];
         }
+        if (p.sq) sq[p.k0 + kk] = qn.h_res[(size_t)p.off + 2 * p.mc * p.k + kk];
+      }
     return 0;
   }
   // S'Y and Y'Y over all rows, once per pair generation (the vectors of the W'V pass are the columns of Y)
@@ -242,12 +262,16 @@
     }
   }
 
+  // log det A over all rows (after qn_root_coef(inv))
+  double qn_logdet_of(bool inv) const {
+    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
+    return (double)nglob * std::log(alpha) + (qn.col > 0 ? qn.root_logsum[inv ? 1 : 0] : 0.0);
+  }
   int qn_logdet(int mode, double *h_logdet) override {
     CHK(qn_ready());
     const bool inv = mode == LBFGSB_QN_H;
     CHK(qn_root_coef(inv));
-    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
-    *h_logdet = (double)nglob * std::log(alpha) + (qn.col > 0 ? qn.root_logsum[inv ? 1 : 0] : 0.0);
+    *h_logdet = qn_logdet_of(inv);
     return 0;
   }
 
@@ -255,10 +279,21 @@
   // the expansion with z generated again (k_qn_draw.hip).  A block of more than one sample starts at an even sample.
   int qn_draw(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean_, double scale, void *out_,
               int64_t ldo) override {
+    return qn_draw_by(mode, k, seed, first, mean_, scale, out_, ldo, nullptr);
+  }
+  // h_logp (k values) or NULL: the log-density of every draw under N(mean, scale^2 A), from z'z of the W'z pass
+  int qn_draw_logpdf(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean_, double scale, void *out_,
+                     int64_t ldo, double *h_logp) override {
+    return qn_draw_by(mode, k, seed, first, mean_, scale, out_, ldo, h_logp);
+  }
+  int qn_draw_by(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean_, double scale, void *out_,
+                 int64_t ldo, double *h_logp) {
     CHK(qn_ready());
     const bool inv = mode == LBFGSB_QN_H;
     CHK(qn_root_coef(inv));
     const int col = qn.col;
+    const double lconst = h_logp ? qn_log_norm(inv, scale) : 0.0;
+    double zz[lbk::QN_KMAX];
     const double ra = std::sqrt(inv ? 1.0 / qn.theta : qn.theta);
     const lbk::WStore<T> w = Wc();
     const T *mean = (const T *)mean_;
@@ -267,10 +302,11 @@
     for (int64_t k0 = 0; k0 < k;) {
       const int64_t s0 = first + k0;
       const int kc = (s0 & 1) ? 1 : (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
-      if (col > 0) {
-        CHK(qn_sums_z(seed, s0, kc, sums.data()));
-        for (int kk = 0; kk < kc; ++kk)
+      if (col > 0 || h_logp) {
+        CHK(qn_sums_z(seed, s0, kc, sums.data(), h_logp ? zz : nullptr));
+        for (int kk = 0; kk < kc && col > 0; ++kk)
           qn_root_map(inv, scale, sums.data() + (size_t)kk * 2 * col, cf.data() + (size_t)kk * 2 * col);
+        for (int kk = 0; kk < kc && h_logp; ++kk) h_logp[k0 + kk] = -0.5 * (lconst + zz[kk]);
       }
       for (int c0 = 0; c0 < std::max(col, 1); c0 += lbk::QN_TILE) {
         const int mc = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col - c0)));
@@ -296,6 +332,52 @@
       k0 += kc;
     }
     return qn_finish();
+  }
+
+  // n_global log 2 pi + 2 n_global log |scale| + log det A (after qn_root_coef(inv))
+  double qn_log_norm(bool inv, double scale) const {
+    return (double)nglob * std::log(6.283185307179586476925) + 2.0 * (double)nglob * std::log(std::fabs(scale)) +
+           qn_logdet_of(inv);
+  }
+  // q_j = (v_j - center)' A (v_j - center) = alpha d'd + p'N p, p = [S, Y]'d: the W'V pass alone, d'd carried along
+  int qn_quad_by(bool inv, int64_t k, const T *v, int64_t ldv, const T *center, double *h_q) {
+    const int col = qn.col;
+    if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
+    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
+    const std::vector<double> dg = qn_dg();
+    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), c((size_t)2 * std::max(col, 1));
+    double dd[lbk::QN_KMAX];
+    for (int64_t k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
+      const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
+      const T *vp[lbk::QN_KMAX];
+      for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (k0 + kk) * ldv;
+      CHK(qn_sums_d(vp, kc, center, sums.data(), dd));
+      for (int kk = 0; kk < kc; ++kk) {
+        const double *sv = sums.data() + (size_t)kk * 2 * col;
+        double t = 0.0;  // p'(N p), S part then Y part, ascending
+        if (col > 0) {
+          CHK(qn_coef(inv, dg.data(), sv, sv + col, c.data(), c.data() + col));
+          for (int i = 0; i < 2 * col; ++i) t = t + sv[i] * c[(size_t)i];
+        }
+        h_q[k0 + kk] = alpha * dd[kk] + t;
+      }
+    }
+    return 0;
+  }
+  int qn_quad(int mode, int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) override {
+    CHK(qn_ready());
+    return qn_quad_by(mode == LBFGSB_QN_H, k, (const T *)v, ldv, (const T *)center, h_q);
+  }
+  // log N(x_j; mean, scale^2 A): the quadratic form of the OTHER mode (A^-1) at x_j - mean, log det A of the root
+  int qn_logpdf(int mode, int64_t k, const void *x, int64_t ldx, const void *mean, double scale,
+                double *h_logp) override {
+    CHK(qn_ready());
+    const bool inv = mode == LBFGSB_QN_H;
+    CHK(qn_root_coef(inv));
+    const double lconst = qn_log_norm(inv, scale);
+    CHK(qn_quad_by(!inv, k, (const T *)x, ldx, (const T *)mean, h_logp));
+    for (int64_t j = 0; j < k; ++j) h_logp[j] = -0.5 * (lconst + h_logp[j] / (scale * scale));
+    return 0;
   }
 
   int qn_apply(int mode, int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) override {

@@ -47,6 +47,7 @@
       integer,parameter,public :: LBFGSB_QN_B = 0, LBFGSB_QN_H = 1
       integer,parameter,public :: LBFGSB_QN_B_SQRT = 4, LBFGSB_QN_H_SQRT = 5   ! lbfgsb_qn_apply only: A^(1/2) v
       public :: lbfgsb_qn_logdet, lbfgsb_qn_draw       ! log det A and draws mean + scale A^(1/2) z, z ~ N(0, I)
+      public :: lbfgsb_qn_quad, lbfgsb_qn_logpdf, lbfgsb_qn_draw_logpdf   ! d'A d and Gaussian log-densities
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
                                                        ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
       ! slots of lbfgsb_kkt's cnt(:) and val(:): the header's LBFGSB_KKT_* indices + 1 (Fortran arrays start at 1)
@@ -173,6 +174,34 @@
             real(c_double),value :: scale
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_draw
+         function lbfgsb_hip_qn_quad(ctx,mode,k,v,ldv,center,q) bind(C,name='lbfgsb_hip_qn_quad') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, v, center
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, ldv
+            real(c_double) :: q(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_quad
+         function lbfgsb_hip_qn_logpdf(ctx,mode,k,x,ldx,mean,scale,logp) bind(C,name='lbfgsb_hip_qn_logpdf') &
+            result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, x, mean
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, ldx
+            real(c_double),value :: scale
+            real(c_double) :: logp(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_logpdf
+         function lbfgsb_hip_qn_draw_logpdf(ctx,mode,k,seed,first,mean,scale,out,ldo,logp) &
+            bind(C,name='lbfgsb_hip_qn_draw_logpdf') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, mean, out
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, seed, first, ldo
+            real(c_double),value :: scale
+            real(c_double) :: logp(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_draw_logpdf
          function lbfgsb_hip_kkt(ctx,x,l,u,nbd,g,tol,pg,mult,status,cnt,val) bind(C,name='lbfgsb_hip_kkt') result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
             type(c_ptr),value :: ctx, x, l, u, nbd, g, pg, mult, status
@@ -469,6 +498,39 @@
       rc = lbfgsb_hip_qn_draw(ctx, int(mode, c_int), int(k, c_int64_t), seed, int(first, c_int64_t), mean, scale, &
                               out, int(ldo, c_int64_t))
       end subroutine lbfgsb_qn_draw
+
+      ! Quadratic forms and Gaussian log-densities of the model (include/lbfgsb_hip.h, same block); every result is
+      ! a host real(c_double) per vector, complete over the rows of all ranks.  lbfgsb_qn_quad: q(j) = (v_j - center)'
+      ! A (v_j - center), mode LBFGSB_QN_B or LBFGSB_QN_H, center may be c_null_ptr.  lbfgsb_qn_logpdf: logp(j) = log
+      ! N(x_j; mean, scale^2 A), mode naming the covariance A.  lbfgsb_qn_draw_logpdf: lbfgsb_qn_draw (the same
+      ! draws bit for bit) and logp(j) = the log-density of draw j.  The last two: at most 64 stored pairs, scale /= 0.
+      subroutine lbfgsb_qn_quad(ctx, mode, k, v, ldv, center, q, rc)
+      type(c_ptr),intent(in) :: ctx, v, center
+      integer,intent(in) :: mode, k, ldv
+      real(c_double),intent(out) :: q(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_quad(ctx, int(mode, c_int), int(k, c_int64_t), v, int(ldv, c_int64_t), center, q)
+      end subroutine lbfgsb_qn_quad
+
+      subroutine lbfgsb_qn_logpdf(ctx, mode, k, x, ldx, mean, scale, logp, rc)
+      type(c_ptr),intent(in) :: ctx, x, mean
+      integer,intent(in) :: mode, k, ldx
+      real(c_double),intent(in) :: scale
+      real(c_double),intent(out) :: logp(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_logpdf(ctx, int(mode, c_int), int(k, c_int64_t), x, int(ldx, c_int64_t), mean, scale, logp)
+      end subroutine lbfgsb_qn_logpdf
+
+      subroutine lbfgsb_qn_draw_logpdf(ctx, mode, k, seed, first, mean, scale, out, ldo, logp, rc)
+      type(c_ptr),intent(in) :: ctx, mean, out
+      integer,intent(in) :: mode, k, first, ldo
+      integer(c_int64_t),intent(in) :: seed
+      real(c_double),intent(in) :: scale
+      real(c_double),intent(out) :: logp(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_draw_logpdf(ctx, int(mode, c_int), int(k, c_int64_t), seed, int(first, c_int64_t), mean, &
+                                     scale, out, int(ldo, c_int64_t), logp)
+      end subroutine lbfgsb_qn_draw_logpdf
 
       ! The active set, the multipliers and the projected gradient (include/lbfgsb_hip.h, "The active set, the bound
       ! multipliers and the projected gradient as device data"): one pass over the device arrays x, l, u, nbd, g of

@@ -389,11 +389,13 @@ class DeviceSolver:
         return val.value
 
     def qn_draw(self, k: int, seed: int, first: int = 0, mean=None, scale: float = 1.0, inverse: bool = True,
-                out=None):
+                out=None, return_logpdf: bool = False):
         """k draws from N(mean, scale^2 A), A = H (inverse=True) or B, as a (k, n) tensor: row j is mean + scale
         A^(1/2) z_(first + j).  The standard normal z_s is generated on the device inside the passes over W; its
         entry for a row depends on (seed, the global row, s) alone -- not on the sharding or on k.  seed: any
-        integer below 2^64.  mean: an (n,) tensor or None.  Returns out."""
+        integer below 2^64.  mean: an (n,) tensor or None.  Returns out; with return_logpdf (out, logp), logp a numpy
+        (k,) array of the draws' log-densities under N(mean, scale^2 A) over all rows of all ranks (the draws are
+        the same bits either way; float32 solvers: the density of the draw before it is rounded on store)."""
         import torch
         dt = torch.float32 if self.real == np.float32 else torch.float64
         if out is None:
@@ -407,12 +409,59 @@ class DeviceSolver:
                 raise ValueError("mean must have shape (n,)")
         ldo = self.n if out.dim() == 1 else out.stride(0)
         self.wait_stream()
+        if return_logpdf:
+            logp = np.zeros(int(k), np.float64)
+            check(self.lib.lbfgsb_hip_qn_draw_logpdf(self.h, capi.QN_H if inverse else capi.QN_B, int(k),
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
+                                                     None if mean is None else mean.data_ptr(), float(scale),
+                                                     out.data_ptr(), ldo,
+                                                     logp.ctypes.data_as(C.POINTER(C.c_double))))
+            self._qn_done()
+            return out, logp
         check(self.lib.lbfgsb_hip_qn_draw(self.h, capi.QN_H if inverse else capi.QN_B, int(k),
                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
                                           None if mean is None else mean.data_ptr(), float(scale), out.data_ptr(),
                                           ldo))
         self._qn_done()
         return out
+
+    def _qn_center(self, c, what):
+        if c is None:
+            return None
+        c = self._qn_vec(c, what)
+        if c.dim() != 1:
+            raise ValueError("%s must have shape (n,)" % what)
+        return c
+
+    def qn_quad(self, v, center=None, inverse: bool = False):
+        """(v_j - center)' A (v_j - center) over all rows of all ranks, A = B (inverse=False) or H, for v of shape (n,)
+        or (k, n): one pass over the pairs per 4 vectors, nothing written on the device.  center: an (n,) tensor or
+        None.  Returns a numpy (k,) array, or a float for a 1-d v.  Any number of stored pairs."""
+        v = self._qn_vec(v, "v")
+        center = self._qn_center(center, "center")
+        k = 1 if v.dim() == 1 else v.shape[0]
+        ldv = self.n if v.dim() == 1 else v.stride(0)
+        q = np.zeros(k, np.float64)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_quad(self.h, capi.QN_H if inverse else capi.QN_B, k, v.data_ptr(), ldv,
+                                          None if center is None else center.data_ptr(),
+                                          q.ctypes.data_as(C.POINTER(C.c_double))))
+        return float(q[0]) if v.dim() == 1 else q
+
+    def qn_logpdf(self, x, mean=None, scale: float = 1.0, inverse: bool = True):
+        """log N(x_j; mean, scale^2 A) over all rows of all ranks, the covariance A = H (inverse=True, as qn_draw's
+        default) or B, for x of shape (n,) or (k, n): the quadratic form of A^-1 by qn_quad's pass and qn_logdet's
+        log det A (at most 64 stored pairs).  Returns a numpy (k,) array, or a float for a 1-d x."""
+        x = self._qn_vec(x, "x")
+        mean = self._qn_center(mean, "mean")
+        k = 1 if x.dim() == 1 else x.shape[0]
+        ldx = self.n if x.dim() == 1 else x.stride(0)
+        lp = np.zeros(k, np.float64)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_logpdf(self.h, capi.QN_H if inverse else capi.QN_B, k, x.data_ptr(), ldx,
+                                            None if mean is None else mean.data_ptr(), float(scale),
+                                            lp.ctypes.data_as(C.POINTER(C.c_double))))
+        return float(lp[0]) if x.dim() == 1 else lp
 
     def qn_operator(self, inverse: bool = True) -> "QnOperator":
         """H (default) or B as a small linear-operator object: hess_inv = sol.qn_operator() after minimize()."""
@@ -755,11 +804,25 @@ class QnOperator:
         v = self.solver.qn_logdet(inverse=self.inverse)
         return 0.5 * v if self.root else v
 
-    def sample(self, k: int, seed: int, first: int = 0, mean=None, scale: float = 1.0):
-        """k draws from N(mean, scale^2 A) as a (k, n) tensor (DeviceSolver.qn_draw)"""
+    def sample(self, k: int, seed: int, first: int = 0, mean=None, scale: float = 1.0, log_prob: bool = False):
+        """k draws from N(mean, scale^2 A) as a (k, n) tensor (DeviceSolver.qn_draw); log_prob=True: (draws, logp)
+        with the draws' log-densities as a numpy (k,) array"""
         if self.root:
             raise ValueError("sample() draws with covariance A: call it on the operator, not on its root")
-        return self.solver.qn_draw(k, seed, first=first, mean=mean, scale=scale, inverse=self.inverse)
+        return self.solver.qn_draw(k, seed, first=first, mean=mean, scale=scale, inverse=self.inverse,
+                                   return_logpdf=log_prob)
+
+    def quad(self, v, center=None):
+        """(v - center)' A (v - center) over all rows of all ranks (DeviceSolver.qn_quad)"""
+        if self.root:
+            raise ValueError("quad() takes B or H, not a square root")
+        return self.solver.qn_quad(v, center=center, inverse=self.inverse)
+
+    def log_prob(self, x, mean=None, scale: float = 1.0):
+        """log N(x; mean, scale^2 A) with this operator as the covariance (DeviceSolver.qn_logpdf)"""
+        if self.root:
+            raise ValueError("log_prob() takes the covariance A: call it on the operator, not on its root")
+        return self.solver.qn_logpdf(x, mean=mean, scale=scale, inverse=self.inverse)
 
     def __matmul__(self, v):
         return self.matvec(v) if v.dim() == 1 else self.matmat(v)
