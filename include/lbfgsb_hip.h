@@ -427,6 +427,22 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  * When, streams, the collective rule and the refusals are qn_apply's.  LBFGSB_E_ARG in addition, changing nothing:
  * NULL v / x / out / h_q / h_logp, k < 1, first < 0, ld < n_local, a mode other than B / H, and for the two
  * log-densities a scale that is 0 or not finite.
+ *
+ * Gram matrices.  qn_quad's values are the diagonal of the k x k matrix (V - center)' A (V - center); qn_gram returns
+ * all of it: the covariance C'H C of k linear functionals under N(x*, H), the Rayleigh-Ritz projection V'B V onto a
+ * subspace, Mahalanobis Gram matrices of points or draws.  With d_a = v_a - center and p_a = [S, Y]'d_a,
+ * d_a'A d_b = alpha d_a'd_b + p_a'N p_b: qn_quad's pass over W per block of 4 vectors, which carries the block's
+ * d_a'd_b (a <= b) along, and for two vectors of different blocks a pass over the vectors alone.  Nothing is written
+ * on the device.
+ *   qn_gram: h_g[a + b*ldg] = (v_a - center)' A (v_b - center) over all n_global rows, a, b < k <=
+ *     LBFGSB_QN_GRAM_MAXK, vector j at v + j*ldv.  h_g is a host array; both triangles are written, entry (b, a) a
+ *     copy of entry (a, b) -- symmetric bit for bit -- and rows a >= k of a column (ldg > k) are left alone.  mode,
+ *     center, the stored pairs and REAL32 contexts as for qn_quad; complete over all ranks, the same bits on each, and
+ *     the call waits for its sums as qn_quad does.  g_aa is qn_quad's formula on the same kind of sums.
+ *     Not offered: a two-operand form U'A V -- stack [U, V] and read the off-diagonal block -- and the root modes
+ *     (the Gram of A^(1/2) is qn_gram of A itself on other vectors; LBFGSB_E_ARG).
+ * When, streams, the collective rule and the refusals are qn_apply's.  LBFGSB_E_ARG in addition, changing nothing:
+ * NULL v / h_g, k < 1, k > LBFGSB_QN_GRAM_MAXK, ldv < n_local, ldg < k, a mode other than B / H.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
@@ -434,6 +450,7 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
 #define LBFGSB_QN_B_SQRT (LBFGSB_QN_SQRT | LBFGSB_QN_B) /* 4: out = B^(1/2) v */
 #define LBFGSB_QN_H_SQRT (LBFGSB_QN_SQRT | LBFGSB_QN_H) /* 5: out = H^(1/2) v */
 #define LBFGSB_QN_ROOT_MAXCOL 64
+#define LBFGSB_QN_GRAM_MAXK 64
 int lbfgsb_hip_qn_apply(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, void *out,
                         int64_t ldo);
 int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out);
@@ -446,6 +463,8 @@ int lbfgsb_hip_qn_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *x
                          double scale, double *h_logp);
 int lbfgsb_hip_qn_draw_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first,
                               const void *mean, double scale, void *out, int64_t ldo, double *h_logp);
+int lbfgsb_hip_qn_gram(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, const void *center,
+                       double *h_g, int64_t ldg);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.

@@ -56,6 +56,8 @@ PROTOTYPES = {
     "lbfgsb_hip_qn_draw": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_uint64, C.c_int64, _vp, C.c_double, _vp,
                                      C.c_int64]),
     "lbfgsb_hip_qn_quad": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(C.c_double)]),
+    "lbfgsb_hip_qn_gram": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(C.c_double),
+                                     C.c_int64]),
     "lbfgsb_hip_qn_logpdf": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.c_double,
                                        C.POINTER(C.c_double)]),
     "lbfgsb_hip_qn_draw_logpdf": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_uint64, C.c_int64, _vp, C.c_double, _vp,

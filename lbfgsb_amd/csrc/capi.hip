@@ -277,6 +277,14 @@ int lbfgsb_hip_qn_draw_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t
     return fail(LBFGSB_E_ARG, "qn_draw_logpdf: scale is 0 or not finite");
   return ctx->qn_draw_logpdf(mode, k, seed, first, mean, scale, out, ldo, h_logp);
 }
+int lbfgsb_hip_qn_gram(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, const void *center,
+                       double *h_g, int64_t ldg) {
+  if (!ctx || !v || !h_g) return fail(LBFGSB_E_ARG, "qn_gram: NULL argument");
+  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_gram: mode");
+  if (k < 1 || k > LBFGSB_QN_GRAM_MAXK) return fail(LBFGSB_E_ARG, "qn_gram: k < 1 or k > LBFGSB_QN_GRAM_MAXK");
+  if (ldv < ctx->n || ldg < k) return fail(LBFGSB_E_ARG, "qn_gram: ldv < n_local or ldg < k");
+  return ctx->qn_vgram(mode, k, v, ldv, center, h_g, ldg);
+}
 
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
                    const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,

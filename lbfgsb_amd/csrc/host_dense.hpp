@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 namespace lbh {
 
@@ -220,6 +221,32 @@ inline void qn_pack_n(int col, int mc, const double *nm, double *np) {
       const double v = ia < 0 || ib < 0 ? 0.0 : nm[ia + (size_t)ib * d];
       np[e++] = a == b ? v : 2.0 * v;
     }
+}
+
+// The Gram matrix of k vectors d_a under A = alpha I + [S, Y] N [S, Y]' from the device's sums (lbfgsb_hip_qn_gram):
+// p holds p_a = [S, Y]'d_a at p[i + a d], d = 2col (S part, then Y part), dtd the upper triangle of D'D at
+// dtd[a + b ldd], a <= b, and coef(stv, ytv, cs, cy) maps p_b to c_b = N p_b (qn_coef_b / qn_coef_h).
+//   g_ab = alpha d_a'd_b + sum_i p_a,i c_b,i,  i ascending (the S part first),  a <= b,
+// and entry (b, a) is a copy of entry (a, b): symmetric bit for bit, and g_aa is the quadratic form's own formula
+// (Solver::qn_quad_by).  Rows a >= k of g's columns (ldg > k) are not touched.  Returns 0 or coef's info, g then as
+// it was.
+template <typename F>
+inline int qn_gram_combine(int col, int k, double alpha, const double *p, const double *dtd, int ldd, F &&coef,
+                           double *g, int64_t ldg) {
+  const int d = 2 * col;
+  std::vector<double> c((size_t)std::max(d, 1) * k);
+  for (int b = 0; b < k && col > 0; ++b) {
+    const double *pb = p + (size_t)b * d;
+    const int info = coef(pb, pb + col, c.data() + (size_t)b * d, c.data() + (size_t)b * d + col);
+    if (info) return info;
+  }
+  for (int b = 0; b < k; ++b)
+    for (int a = 0; a <= b; ++a) {
+      double t = 0.0;
+      for (int i = 0; i < d; ++i) t = t + p[i + (size_t)a * d] * c[i + (size_t)b * d];
+      g[a + b * ldg] = g[b + a * ldg] = alpha * dtd[a + (size_t)b * ldd] + t;
+    }
+  return 0;
 }
 
 // ---- the square root and the log-determinant of the model (lbfgsb_hip_qn_apply's root modes, qn_logdet, qn_draw) ----

@@ -5,6 +5,8 @@
 // with the 2col x 2col matrices N formed on the host (host_dense.hpp, qn_coef_b / qn_coef_h).  The passes:
 //   qn_wtv     [S'v; Y'v] for K vectors at once (every W entry read once per block of K vectors);
 //   qn_wtd     the same for d = v - center with d'd carried along: the one pass of a quadratic form d'A d;
+//   qn_wtg     qn_wtd with the block's whole Gram d_a'd_b, a <= b, carried along (lbfgsb_hip_qn_gram, section 10d);
+//   qn_dtd     d_a'd_b for a in one block of vectors and b in another: vectors only, nothing of W;
 //   qn_expand  out_j = alpha src_j + S cs_j + Y cy_j (coefficients as kernel arguments);
 //   qn_diag    out_i = alpha + r_i' N r_i,  r_i = row i of [S, Y], N in LDS (upper triangle, off-diagonal doubled).
 // None of them writes W: they read it in the layout it is in (natural order, or the tile-local layout of k_layout.hip
@@ -20,15 +22,18 @@ namespace lbk {
 // VSLOT: vector row i is read at the SLOT of row i (the vectors are columns of W themselves: the Gram).
 // CEN: the vectors are d_kk = v_kk - center, formed in fp64 in registers (no center: neither a load nor an address).
 // DD: K more sums d_kk'd_kk in the slots 2MC K + kk (the first column tile's launch of a quadratic form carries them).
-// The plain pass (qn_wtv_kernel) is the body with both off.
-template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT, bool CEN, bool DD>
+// GG: instead of them the K (K + 1) / 2 sums d_a'd_b, a <= b, row by row of the upper triangle from slot 2MC K on
+// (at K = 1 that is DD itself: launch_qn_wtg hands it to qn_wtd_kernel).
+// The plain pass (qn_wtv_kernel) is the body with all three off.
+template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT, bool CEN, bool DD, bool GG = false>
 __device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
                                             const T *__restrict__ zero, int64_t ldw, int m, int head, int col, int c0,
                                             const uint64_t *__restrict__ lmask, const QnVecs<T> &v,
                                             const T *__restrict__ center, double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
-  static_assert(!VSLOT || !(CEN || DD), "a center and the squared norm belong to vectors in natural order");
-  constexpr int NW = 2 * MC * K, NACC = NW + (DD ? K : 0);
+  static_assert(!VSLOT || !(CEN || DD || GG), "a center and the squared norm belong to vectors in natural order");
+  static_assert(!(DD && GG), "the Gram holds the squared norms");
+  constexpr int NW = 2 * MC * K, NACC = NW + (GG ? K * (K + 1) / 2 : DD ? K : 0);
   double acc[NACC];
 #pragma unroll
   for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
@@ -70,6 +75,15 @@ __device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws,
 #pragma unroll
         for (int w = 0; w < W; ++w) acc[NW + kk] += vv[kk][w] * vv[kk][w];
     }
+    if constexpr (GG) {
+      int e = NW;
+#pragma unroll
+      for (int ka = 0; ka < K; ++ka)
+#pragma unroll
+        for (int kb = ka; kb < K; ++kb, ++e)
+#pragma unroll
+          for (int w = 0; w < W; ++w) acc[e] += vv[ka][w] * vv[kb][w];
+    }
   });
   block_reduce_store<NACC>(acc, NACC, 0, 0, part, MAX_BLOCKS);
 }
@@ -90,6 +104,54 @@ __global__ __launch_bounds__(BLOCK) void qn_wtd_kernel(int64_t n, const T *__res
                                                        int col, int c0, const uint64_t *__restrict__ lmask,
                                                        QnVecs<T> v, const T *__restrict__ center, double *part) {
   qn_wtv_body<T, MC, K, V, CW, false, NT, CEN, DD>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, center, part);
+}
+
+// the W'V pass of a Gram matrix (lbfgsb_hip_qn_gram): the first tile's launch, the block's d_a'd_b along (K >= 2)
+template <typename T, int MC, int K, int V, bool CW, bool NT, bool CEN>
+__global__ __launch_bounds__(BLOCK) void qn_wtg_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
+                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
+                                                       int col, int c0, const uint64_t *__restrict__ lmask,
+                                                       QnVecs<T> v, const T *__restrict__ center, double *part) {
+  qn_wtv_body<T, MC, K, V, CW, false, NT, CEN, false, true>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, center,
+                                                            part);
+}
+
+// sums: slot ia * KB + ib = d_ia'd_ib, d_ia = a_ia - center of one block of vectors, d_ib = b_ib - center of another:
+// the entries of D'D that no W'd launch holds.  (KA + KB + 1) reals per row, natural row order, nothing written.
+template <typename T, int KA, int KB, int V, bool NT, bool CEN>
+__global__ __launch_bounds__(BLOCK) void qn_dtd_kernel(int64_t n, QnVecs<T> a, QnVecs<T> b,
+                                                       const T *__restrict__ center, double *part) {
+  constexpr int NACC = KA * KB;
+  double acc[NACC];
+#pragma unroll
+  for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+  for_rows<T, V>(n, [&](int64_t i, auto wt) {
+    constexpr int W = decltype(wt)::value;
+    double x[KA][W], y[KB][W];
+#pragma unroll
+    for (int ia = 0; ia < KA; ++ia) ldx<W, NT>(a.p[ia] + i, x[ia]);
+#pragma unroll
+    for (int ib = 0; ib < KB; ++ib) ldx<W, NT>(b.p[ib] + i, y[ib]);
+    double cc[CEN ? W : 1];
+    if constexpr (CEN) {
+      ldx<W, NT>(center + i, cc);
+      __builtin_amdgcn_sched_barrier(0);  // (the differences behind every load of the trip, as in qn_wtv_body)
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+#pragma unroll
+        for (int ia = 0; ia < KA; ++ia) x[ia][w] -= cc[w];
+#pragma unroll
+        for (int ib = 0; ib < KB; ++ib) y[ib][w] -= cc[w];
+      }
+    }
+#pragma unroll
+    for (int ia = 0; ia < KA; ++ia)
+#pragma unroll
+      for (int ib = 0; ib < KB; ++ib)
+#pragma unroll
+        for (int w = 0; w < W; ++w) acc[ia * KB + ib] += x[ia][w] * y[ib][w];
+  });
+  block_reduce_store<NACC>(acc, NACC, 0, 0, part, MAX_BLOCKS);
 }
 
 // res[k] = sum over the workgroups' partials of slot k, in a fixed order (one workgroup per slot)
@@ -240,6 +302,66 @@ hipError_t launch_qn_wtd(const Queue &q, int64_t n, WStore<T> w, int head, int c
 }
 
 template <typename T>
+hipError_t launch_qn_wtg(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                         QnVecs<T> v, const T *center, double *part, double *res) {
+  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
+  // (one vector: its Gram is its squared norm -- qn_wtd's own kernel, no second instantiation of it)
+  if (k == 1) return launch_qn_wtd<T>(q, n, w, head, col, c0, mc, k, v, center, true, part, res);
+  // (rows per lane as qn_wtd: two at 5 columns and K = 2 only)
+  bool vec2 = 2 * mc * k <= 20 && (!center || aligned_for(center, 2));
+  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
+  int g = 0;
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT,
+      QN_DISPATCH_BOOL(center != nullptr, CEN, {
+    if constexpr (K >= 2) {
+      auto kern = qn_wtg_kernel<T, MC, K, V, CW, NT, CEN>;
+      g = grid_for_w(q, n, V, (const void *)kern);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
+                         w.lmask, v, center, part);
+    }
+  })))));
+  if (g == 0) return hipErrorInvalidValue;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_qn_finalize(q, part, g, 2 * mc * k + k * (k + 1) / 2, res);
+}
+
+#define QN_DISPATCH_KAB(k, NAME, ...) \
+  do {                                \
+    if ((k) == 1) {                   \
+      constexpr int NAME = 1;         \
+      __VA_ARGS__;                    \
+    } else if ((k) == 2) {            \
+      constexpr int NAME = 2;         \
+      __VA_ARGS__;                    \
+    } else {                          \
+      constexpr int NAME = 4;         \
+      __VA_ARGS__;                    \
+    }                                 \
+  } while (0)
+
+template <typename T>
+hipError_t launch_qn_dtd(const Queue &q, int64_t n, QnVecs<T> a, int ka, QnVecs<T> b, int kb, const T *center,
+                         double *part, double *res) {
+  if ((ka != 1 && ka != 2 && ka != 4) || (kb != 1 && kb != 2 && kb != 4)) return hipErrorInvalidValue;
+  bool vec2 = !center || aligned_for(center, 2);
+  for (int kk = 0; kk < ka; ++kk) vec2 = vec2 && aligned_for(a.p[kk], 2);
+  for (int kk = 0; kk < kb; ++kk) vec2 = vec2 && aligned_for(b.p[kk], 2);
+  int g = 0;
+  QN_DISPATCH_KAB(ka, KA, QN_DISPATCH_KAB(kb, KB, QN_DISPATCH_BOOL(vec2, V2, QN_DISPATCH_BOOL(q.nt, NT,
+      QN_DISPATCH_BOOL(center != nullptr, CEN, {
+    auto kern = qn_dtd_kernel<T, KA, KB, V2 ? 2 : 1, NT, CEN>;
+    g = grid_for_w(q, n, V2 ? 2 : 1, (const void *)kern);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, a, b, center, part);
+  })))));
+  if (g == 0) return hipErrorInvalidValue;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_qn_finalize(q, part, g, ka * kb, res);
+}
+#undef QN_DISPATCH_KAB
+
+template <typename T>
 hipError_t launch_qn_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                             const double *coef, double alpha, QnVecs<T> src, QnOuts<T> out) {
   if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
@@ -284,6 +406,10 @@ hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int 
                                        bool, double *, double *);                                                 \
   template hipError_t launch_qn_wtd<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
                                        const T *, bool, double *, double *);                                      \
+  template hipError_t launch_qn_wtg<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
+                                       const T *, double *, double *);                                            \
+  template hipError_t launch_qn_dtd<T>(const Queue &, int64_t, QnVecs<T>, int, QnVecs<T>, int, const T *,       \
+                                       double *, double *);                                                       \
   template hipError_t launch_qn_expand<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,          \
                                           const double *, double, QnVecs<T>, QnOuts<T>);                         \
   template hipError_t launch_qn_diag<T>(const Queue &, int64_t, WStore<T>, int, int, const double *, double, T *);

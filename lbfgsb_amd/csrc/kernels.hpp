@@ -537,6 +537,16 @@ hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int c
 template <typename T>
 hipError_t launch_qn_wtd(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                          QnVecs<T> v, const T *center, bool dd, double *part, double *res);
+// The same with the block's whole Gram along: k (k + 1) / 2 sums d_a'd_b, a <= b, row by row of the upper triangle in
+// res[2 mc k ...] -- the first tile's launch of a Gram matrix (lbfgsb_hip_qn_gram); k = 1 is launch_qn_wtd with dd
+template <typename T>
+hipError_t launch_qn_wtg(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                         QnVecs<T> v, const T *center, double *part, double *res);
+// res[ia * kb + ib] = (a_ia - center)'(b_ib - center), ka, kb in {1, 2, 4} (center may be NULL): the entries of D'D
+// across two blocks of vectors, from the vectors alone
+template <typename T>
+hipError_t launch_qn_dtd(const Queue &q, int64_t n, QnVecs<T> a, int ka, QnVecs<T> b, int kb, const T *center,
+                         double *part, double *res);
 // res[k] = the sum of slot k's nblocks partials, k < nslots, in a fixed order (launch_qn_wtv / launch_qn_wtz end so)
 hipError_t launch_qn_finalize(const Queue &q, const double *part, int nblocks, int nslots, double *res);
 // out_k = alpha src_k + [S, Y](:, tile) coef[k * 2 mc ...] (src_k may be out_k: the second and later tiles)

@@ -164,6 +164,8 @@ struct lbfgsb_hip_ctx {
                         double *h_logp) = 0;
   virtual int qn_draw_logpdf(int mode, int64_t k, uint64_t seed, int64_t first, const void *mean, double scale,
                              void *out, int64_t ldo, double *h_logp) = 0;
+  virtual int qn_vgram(int mode, int64_t k, const void *v, int64_t ldv, const void *center, double *h_g,
+                       int64_t ldg) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

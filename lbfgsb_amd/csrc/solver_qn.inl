@@ -2,7 +2,8 @@
 // limited-memory curvature model B and its inverse H = B^-1 as device operators (lbfgsb_hip_qn_apply,
 // lbfgsb_hip_qn_diag; k_qn.hip has the kernels, host_dense.hpp the 2col x 2col algebra), their
 // symmetric square roots, log-determinants and draws (lbfgsb_hip_qn_logdet, lbfgsb_hip_qn_draw; k_qn_draw.hip), and
-// quadratic forms and Gaussian log-densities (lbfgsb_hip_qn_quad, qn_logpdf, qn_draw_logpdf).
+// quadratic forms and Gaussian log-densities (lbfgsb_hip_qn_quad, qn_logpdf, qn_draw_logpdf),
+// and Gram matrices on blocks of vectors (lbfgsb_hip_qn_gram; section 10d).
 //
 // The entries read the pairs of the last return (or import) and nothing else of the iteration's state changes:
 // W is read in the layout it is in (Wc(), never W()), the sums go through buffers of their own (never q.d_part /
@@ -27,8 +28,10 @@
     double *h_n = nullptr;      // pinned staging of a packed N
     std::vector<double> h_res, h_all;
   } qn;
-  // sums of one vector block: 2 (col + QN_TILE) per vector, and its squared norm (quadratic forms, draw densities)
-  static constexpr int QN_RES = (2 * (LBFGSB_MAX_M + lbk::QN_TILE) + 1) * lbk::QN_KMAX;
+  // sums of one vector block: 2 (col + QN_TILE) per vector, and its squared norms (quadratic forms, draw densities)
+  // or the upper triangle of its Gram (Gram matrices)
+  static constexpr int QN_RES =
+      2 * (LBFGSB_MAX_M + lbk::QN_TILE) * lbk::QN_KMAX + lbk::QN_KMAX * (lbk::QN_KMAX + 1) / 2;
   static constexpr int QN_NP = 64 * 65 / 2;                                         // packed N at 32 pairs
 
   // save_locals: what the entries will read until the next return
@@ -109,7 +112,13 @@
   struct QnPiece {  // one launch of a W'V pass: the vectors k0 .. k0 + k - 1 on the column tile at c0, sums at off
     int c0, mc, k0, k, off;
     bool sq;  // the launch carries the k squared norms too, behind its 2 mc k sums (the first tile, when asked for)
+              // -- of a Gram matrix the k (k + 1) / 2 sums d_a'd_b of the piece, a <= b, row by row
   };
+  // the vectors of a block that the next launch on a tile of capacity mc takes: 4 / 2 / 1, 3 -> 2 + 1
+  static int qn_piece_k(int left, int mc) {
+    const int k = std::min(left, lbk::qn_kmax(mc));
+    return k == 3 ? 2 : k;
+  }
   // [S'v_k; Y'v_k] for kc <= QN_KMAX vectors -> out[k * 2 col + i] (i < col: S, else Y), all ranks reduced
   int qn_sums(const T *const *v, int kc, bool vslot, double *out) {
     const lbk::WStore<T> w = Wc();
@@ -142,10 +151,30 @@
                          "qn_wtd");
     });
   }
+  // the same with the Gram of every piece of the first tile: gr[a + b QN_KMAX] = d_a'd_b for a <= b of one piece
+  // (the squared norms among them); entries across two pieces are left as they are (qn_sums_dd)
+  int qn_sums_g(const T *const *v, int kc, const T *center, double *out, double *gr) {
+    const lbk::WStore<T> w = Wc();
+    return qn_sums_by(
+        kc, out, gr,
+        [&](const QnPiece &p) {
+          lbk::QnVecs<T> vv{};
+          for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
+          if (p.sq)
+            return qn_launched(lbk::launch_qn_wtg<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, center, qn.d_part,
+                                                     qn.d_res + p.off),
+                               "qn_wtg");
+          return qn_launched(lbk::launch_qn_wtd<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, center, false,
+                                                   qn.d_part, qn.d_res + p.off),
+                             "qn_wtd");
+        },
+        true);
+  }
   // sq (kc values) or NULL: the vectors' squared norms, carried by the launches of the first column tile -- with no
-  // stored pair by launches on an empty tile, which read the zero line and nothing of W
+  // stored pair by launches on an empty tile, which read the zero line and nothing of W.  gram: sq is a QN_KMAX x
+  // QN_KMAX matrix instead and the first tile's launches carry the upper triangle of each piece's Gram
   template <typename L>
-  int qn_sums_by(int kc, double *out, double *sq, L &&launch) {
+  int qn_sums_by(int kc, double *out, double *sq, L &&launch, bool gram = false) {
     const int col = qn.col;
     using Piece = QnPiece;
     std::vector<Piece> pieces;
@@ -153,15 +182,15 @@
     for (int c0 = 0; c0 < std::max(col, sq ? 1 : 0); c0 += lbk::QN_TILE) {
       const int mc = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col - c0)));
       for (int k0 = 0; k0 < kc;) {  // blocks of 4 / 2 / 1 vectors the tile's kernels take
-        int k = std::min(kc - k0, lbk::qn_kmax(mc));
-        if (k == 3) k = 2;
+        const int k = qn_piece_k(kc - k0, mc);
         const bool carry = sq && c0 == 0;
         pieces.push_back(Piece{c0, mc, k0, k, off, carry});
-        off += 2 * mc * k + (carry ? k : 0);
+        off += 2 * mc * k + (carry ? (gram ? k * (k + 1) / 2 : k) : 0);
         k0 += k;
       }
     }
-    // (<= (2 (col + QN_TILE) + 1) kc <= QN_RES for every col <= LBFGSB_MAX_M; checked before anything is written)
+    // (<= 2 (col + QN_TILE) kc + kc (kc + 1) / 2 <= QN_RES for every col <= LBFGSB_MAX_M; checked before anything is
+    //  written)
     if (off > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");
     for (const Piece &p : pieces) CHK(launch(p));
     CHK(qn_reduce(off));
@@ -172,7 +201,13 @@
           o[p.c0 + j] = qn.h_res[(size_t)p.off + kk * 2 * p.mc + j];
           o[col + p.c0 + j] = qn.h_res[(size_t)p.off + kk * 2 * p.mc + p.mc + j];
         }
-        if (p.sq) sq[p.k0 + kk] = qn.h_res[(size_t)p.off + 2 * p.mc * p.k + kk];
+        if (p.sq && !gram) sq[p.k0 + kk] = qn.h_res[(size_t)p.off + 2 * p.mc * p.k + kk];
+      }
+    for (const Piece &p : pieces)
+      if (p.sq && gram) {
+        const double *r = qn.h_res.data() + (size_t)p.off + 2 * p.mc * p.k;
+        for (int a = 0; a < p.k; ++a)
+          for (int b = a; b < p.k; ++b) sq[(p.k0 + a) + (size_t)(p.k0 + b) * lbk::QN_KMAX] = *r++;
       }
     return 0;
   }
@@ -363,6 +398,74 @@
       }
     }
     return 0;
+  }
+  // d_a'd_b for every a of one piece and b of a later one: one vectors-only launch per pair of pieces, all of them
+  // back to back and fetched with one wait (fewer than k^2 / 2 <= 2048 sums: they fit the result buffer together).
+  // pc: (first vector, width) of the pieces; dtd[a + b ldd], a < b
+  int qn_sums_dd(const T *v, int64_t ldv, const T *center, const std::vector<std::pair<int, int>> &pc, double *dtd,
+                 int ldd) {
+    struct Job {
+      int a0, ka, b0, kb, off;
+    };
+    std::vector<Job> jobs;
+    int off = 0;
+    for (size_t ia = 0; ia < pc.size(); ++ia)
+      for (size_t ib = ia + 1; ib < pc.size(); ++ib) {
+        jobs.push_back(Job{pc[ia].first, pc[ia].second, pc[ib].first, pc[ib].second, off});
+        off += pc[ia].second * pc[ib].second;
+      }
+    if (jobs.empty()) return 0;
+    if (off > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");  // (before any launch)
+    for (const Job &j : jobs) {
+      lbk::QnVecs<T> va{}, vb{};
+      for (int kk = 0; kk < j.ka; ++kk) va.p[kk] = v + (int64_t)(j.a0 + kk) * ldv;
+      for (int kk = 0; kk < j.kb; ++kk) vb.p[kk] = v + (int64_t)(j.b0 + kk) * ldv;
+      CHK(qn_launched(lbk::launch_qn_dtd<T>(q, n, va, j.ka, vb, j.kb, center, qn.d_part, qn.d_res + j.off),
+                      "qn_dtd"));
+    }
+    CHK(qn_reduce(off));
+    for (const Job &j : jobs)
+      for (int ia = 0; ia < j.ka; ++ia)
+        for (int ib = 0; ib < j.kb; ++ib)
+          dtd[(j.a0 + ia) + (size_t)(j.b0 + ib) * ldd] = qn.h_res[(size_t)j.off + ia * j.kb + ib];
+    return 0;
+  }
+  // G = (V - c)' A (V - c): per block of QN_KMAX vectors the W'd pass with the Gram of each piece along (p_a and the
+  // d_a'd_b inside a piece), across pieces the vectors-only pass, then g_ab = alpha d_a'd_b + p_a'(N p_b) on the host
+  int qn_vgram(int mode, int64_t k_, const void *v_, int64_t ldv, const void *center_, double *h_g,
+               int64_t ldg) override {
+    CHK(qn_ready());
+    const bool inv = mode == LBFGSB_QN_H;
+    const int col = qn.col, k = (int)k_, d = 2 * col;
+    if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
+    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
+    const T *v = (const T *)v_, *center = (const T *)center_;
+    std::vector<double> p((size_t)std::max(d, 1) * k), dtd((size_t)k * k, 0.0);
+    std::vector<std::pair<int, int>> pc;
+    const int mc0 = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col)));
+    for (int k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
+      const int kc = std::min(lbk::QN_KMAX, k - k0);
+      const T *vp[lbk::QN_KMAX];
+      for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (int64_t)(k0 + kk) * ldv;
+      double gr[lbk::QN_KMAX * lbk::QN_KMAX] = {};
+      CHK(qn_sums_g(vp, kc, center, p.data() + (size_t)k0 * d, gr));
+      for (int j0 = 0; j0 < kc;) {  // the pieces qn_sums_by has formed on the first tile
+        const int kb = qn_piece_k(kc - j0, mc0);
+        pc.emplace_back(k0 + j0, kb);
+        for (int a = 0; a < kb; ++a)
+          for (int b = a; b < kb; ++b)
+            dtd[(k0 + j0 + a) + (size_t)(k0 + j0 + b) * k] = gr[(j0 + a) + (size_t)(j0 + b) * lbk::QN_KMAX];
+        j0 += kb;
+      }
+    }
+    CHK(qn_sums_dd(v, ldv, center, pc, dtd.data(), k));
+    const std::vector<double> dg = qn_dg();
+    return lbh::qn_gram_combine(
+        col, k, alpha, p.data(), dtd.data(), k,
+        [&](const double *stv, const double *ytv, double *cs, double *cy) {
+          return qn_coef(inv, dg.data(), stv, ytv, cs, cy);
+        },
+        h_g, ldg);
   }
   int qn_quad(int mode, int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) override {
     CHK(qn_ready());

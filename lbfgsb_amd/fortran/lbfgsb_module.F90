@@ -48,6 +48,7 @@
       integer,parameter,public :: LBFGSB_QN_B_SQRT = 4, LBFGSB_QN_H_SQRT = 5   ! lbfgsb_qn_apply only: A^(1/2) v
       public :: lbfgsb_qn_logdet, lbfgsb_qn_draw       ! log det A and draws mean + scale A^(1/2) z, z ~ N(0, I)
       public :: lbfgsb_qn_quad, lbfgsb_qn_logpdf, lbfgsb_qn_draw_logpdf   ! d'A d and Gaussian log-densities
+      public :: lbfgsb_qn_gram                          ! the k x k matrix (V - center)' A (V - center)
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
                                                        ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
       ! slots of lbfgsb_kkt's cnt(:) and val(:): the header's LBFGSB_KKT_* indices + 1 (Fortran arrays start at 1)
@@ -182,6 +183,14 @@
             real(c_double) :: q(*)
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_quad
+         function lbfgsb_hip_qn_gram(ctx,mode,k,v,ldv,center,g,ldg) bind(C,name='lbfgsb_hip_qn_gram') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, v, center
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, ldv, ldg
+            real(c_double) :: g(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_gram
          function lbfgsb_hip_qn_logpdf(ctx,mode,k,x,ldx,mean,scale,logp) bind(C,name='lbfgsb_hip_qn_logpdf') &
             result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
@@ -511,6 +520,17 @@
       integer,intent(out) :: rc
       rc = lbfgsb_hip_qn_quad(ctx, int(mode, c_int), int(k, c_int64_t), v, int(ldv, c_int64_t), center, q)
       end subroutine lbfgsb_qn_quad
+
+      ! g(a, b) = (v_a - center)' A (v_b - center), a, b <= k <= 64, a host array of leading dimension ldg >= k:
+      ! both triangles, symmetric bit for bit; its diagonal is lbfgsb_qn_quad's (include/lbfgsb_hip.h, "Gram matrices")
+      subroutine lbfgsb_qn_gram(ctx, mode, k, v, ldv, center, g, ldg, rc)
+      type(c_ptr),intent(in) :: ctx, v, center
+      integer,intent(in) :: mode, k, ldv, ldg
+      real(c_double),intent(inout) :: g(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_gram(ctx, int(mode, c_int), int(k, c_int64_t), v, int(ldv, c_int64_t), center, g, &
+                              int(ldg, c_int64_t))
+      end subroutine lbfgsb_qn_gram
 
       subroutine lbfgsb_qn_logpdf(ctx, mode, k, x, ldx, mean, scale, logp, rc)
       type(c_ptr),intent(in) :: ctx, x, mean

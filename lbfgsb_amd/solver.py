@@ -448,6 +448,23 @@ class DeviceSolver:
                                           q.ctypes.data_as(C.POINTER(C.c_double))))
         return float(q[0]) if v.dim() == 1 else q
 
+    def qn_gram(self, v, center=None, inverse: bool = False):
+        """The k x k matrix (v_a - center)' A (v_b - center) over all rows of all ranks, A = B (inverse=False) or H,
+        for v of shape (k, n), k <= 64 (a 1-d v gives (1, 1)): qn_quad's pass with the d_a'd_b of each block of 4
+        vectors carried along, and a pass over the vectors alone for two vectors of different blocks.  Returns a
+        numpy (k, k) float64 array, symmetric bit for bit; its diagonal is qn_quad's.  With the rows of v the
+        functionals c_j and inverse=True it is their covariance C'H C under the Laplace posterior N(x*, H)."""
+        v = self._qn_vec(v, "v")
+        center = self._qn_center(center, "center")
+        k = 1 if v.dim() == 1 else v.shape[0]
+        ldv = self.n if v.dim() == 1 else v.stride(0)
+        g = np.zeros((k, k), np.float64)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_gram(self.h, capi.QN_H if inverse else capi.QN_B, k, v.data_ptr(), ldv,
+                                          None if center is None else center.data_ptr(),
+                                          g.ctypes.data_as(C.POINTER(C.c_double)), k))
+        return g
+
     def qn_logpdf(self, x, mean=None, scale: float = 1.0, inverse: bool = True):
         """log N(x_j; mean, scale^2 A) over all rows of all ranks, the covariance A = H (inverse=True, as qn_draw's
         default) or B, for x of shape (n,) or (k, n): the quadratic form of A^-1 by qn_quad's pass and qn_logdet's
@@ -817,6 +834,12 @@ class QnOperator:
         if self.root:
             raise ValueError("quad() takes B or H, not a square root")
         return self.solver.qn_quad(v, center=center, inverse=self.inverse)
+
+    def gram(self, v, center=None):
+        """(v_a - center)' A (v_b - center) as a numpy (k, k) array (DeviceSolver.qn_gram)"""
+        if self.root:
+            raise ValueError("gram() takes B or H, not a square root")
+        return self.solver.qn_gram(v, center=center, inverse=self.inverse)
 
     def log_prob(self, x, mean=None, scale: float = 1.0):
         """log N(x; mean, scale^2 A) with this operator as the covariance (DeviceSolver.qn_logpdf)"""
