@@ -71,9 +71,21 @@ enum {
                                 32768 breakpoints within reach) by a full sort + prefix scans of the
                                 walk's state on the device, the clamp included (a scan over the maps
                                 x -> max(B, x + A)) -- again the reference's result in exact
-                                arithmetic.  With several ranks the records of all breakpoints are
-                                all-gathered and every rank runs the same (bitwise-reproducible)
-                                scans.  Short walks always replay the walk exactly. */
+                                arithmetic, EXCEPT for the order of equal breakpoints: the search
+                                takes them in (t, variable index) order and has none of the walk's
+                                detection of a stop inside a group of equal t (tie_split / grp_sens,
+                                see LBFGSB_F_EXACT_TIES below).  A group crossed whole gives the same
+                                sums in any order; when the stop falls INSIDE a group, the members
+                                with the lowest indices are the ones fixed, where the reference fixes
+                                those its heap (hpsolb, :2079) pops first -- which members, and when
+                                their rows of W differ how many, may then differ.  Such a call is not
+                                counted by lbfgsb_hip_tie_splits and not replayed: a documented limit
+                                of the opt-in mode (the col = 0 closed form fixes every t_j <= 1/theta
+                                and has no such case).  With several ranks the records of all
+                                breakpoints are all-gathered and every rank runs the same
+                                (bitwise-reproducible) scans.  Short walks always replay the walk
+                                exactly.  tests/test_gpu_pgcp_door.py holds one call of either form
+                                against an extended-precision walk. */
   LBFGSB_F_EXACT_TIES = 16,  /* accepted and ignored: this IS the default behaviour now (round 3).
                                 Breakpoints with EQUAL t reach the walk in variable order; the reference
                                 pops them in the order of hpsolb's heap (src/lbfgsb.f90:2079, used at

@@ -11,6 +11,9 @@ routine into the next.
 Bars: integers, iwhere, Index, Indx2, task strings, copies (t, r, the new W column) bit-exact; sums over
 n rows 1e-12 of their scale (other summation order); results of the 2m x 2m solves 1e-9 relative to the
 largest entry (conditioning, as in tests/test_gpu_parity.py).
+
+The Cauchy door of a context created with parallel_gcp=True (the opt-in search: sort + scans, the col = 0 closed form
+and its guard) is covered in tests/test_gpu_pgcp_door.py, against the extended-precision walk of tests/_gcp_truth.py.
 """
 import numpy as np
 import pytest
