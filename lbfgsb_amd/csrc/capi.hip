@@ -226,28 +226,31 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
   return ctx->import_state(wa, iwa, isave);
 }
 
+// the model or its inverse: the modes of every entry below (qn_apply takes their square roots too)
+static bool qn_mode_ok(int mode) { return mode == LBFGSB_QN_B || mode == LBFGSB_QN_H; }
+
 int lbfgsb_hip_qn_apply(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, void *out,
                         int64_t ldo) {
   if (!ctx || !v || !out) return fail(LBFGSB_E_ARG, "qn_apply: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H && mode != LBFGSB_QN_B_SQRT && mode != LBFGSB_QN_H_SQRT)
+  if (!qn_mode_ok(mode) && mode != LBFGSB_QN_B_SQRT && mode != LBFGSB_QN_H_SQRT)
     return fail(LBFGSB_E_ARG, "qn_apply: mode");
   if (k < 1 || ldv < ctx->n || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_apply: k < 1 or ld < n_local");
   return ctx->qn_apply(mode, k, v, ldv, out, ldo);
 }
 int lbfgsb_hip_qn_diag(lbfgsb_hip_ctx *ctx, int mode, void *out) {
   if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_diag: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_diag: mode");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_diag: mode");
   return ctx->qn_diag(mode, out);
 }
 int lbfgsb_hip_qn_logdet(lbfgsb_hip_ctx *ctx, int mode, double *h_logdet) {
   if (!ctx || !h_logdet) return fail(LBFGSB_E_ARG, "qn_logdet: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_logdet: mode");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_logdet: mode");
   return ctx->qn_logdet(mode, h_logdet);
 }
 int lbfgsb_hip_qn_draw(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first, const void *mean,
                        double scale, void *out, int64_t ldo) {
   if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_draw: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_draw: mode");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_draw: mode");
   if (k < 1 || first < 0 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_draw: k < 1, first < 0 or ldo < n_local");
   if (!std::isfinite(scale)) return fail(LBFGSB_E_ARG, "qn_draw: scale is not finite");
   return ctx->qn_draw(mode, k, seed, first, mean, scale, out, ldo);
@@ -255,14 +258,14 @@ int lbfgsb_hip_qn_draw(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, 
 int lbfgsb_hip_qn_quad(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, const void *center,
                        double *h_q) {
   if (!ctx || !v || !h_q) return fail(LBFGSB_E_ARG, "qn_quad: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_quad: mode");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_quad: mode");
   if (k < 1 || ldv < ctx->n) return fail(LBFGSB_E_ARG, "qn_quad: k < 1 or ldv < n_local");
   return ctx->qn_quad(mode, k, v, ldv, center, h_q);
 }
 int lbfgsb_hip_qn_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *x, int64_t ldx, const void *mean,
                          double scale, double *h_logp) {
   if (!ctx || !x || !h_logp) return fail(LBFGSB_E_ARG, "qn_logpdf: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_logpdf: mode");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_logpdf: mode");
   if (k < 1 || ldx < ctx->n) return fail(LBFGSB_E_ARG, "qn_logpdf: k < 1 or ldx < n_local");
   if (!std::isfinite(scale) || scale == 0.0) return fail(LBFGSB_E_ARG, "qn_logpdf: scale is 0 or not finite");
   return ctx->qn_logpdf(mode, k, x, ldx, mean, scale, h_logp);
@@ -270,7 +273,7 @@ int lbfgsb_hip_qn_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *x
 int lbfgsb_hip_qn_draw_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t seed, int64_t first,
                               const void *mean, double scale, void *out, int64_t ldo, double *h_logp) {
   if (!ctx || !out || !h_logp) return fail(LBFGSB_E_ARG, "qn_draw_logpdf: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_draw_logpdf: mode");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_draw_logpdf: mode");
   if (k < 1 || first < 0 || ldo < ctx->n)
     return fail(LBFGSB_E_ARG, "qn_draw_logpdf: k < 1, first < 0 or ldo < n_local");
   if (!std::isfinite(scale) || scale == 0.0)
@@ -280,7 +283,7 @@ int lbfgsb_hip_qn_draw_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t
 int lbfgsb_hip_qn_gram(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, const void *center,
                        double *h_g, int64_t ldg) {
   if (!ctx || !v || !h_g) return fail(LBFGSB_E_ARG, "qn_gram: NULL argument");
-  if (mode != LBFGSB_QN_B && mode != LBFGSB_QN_H) return fail(LBFGSB_E_ARG, "qn_gram: mode");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_gram: mode");
   if (k < 1 || k > LBFGSB_QN_GRAM_MAXK) return fail(LBFGSB_E_ARG, "qn_gram: k < 1 or k > LBFGSB_QN_GRAM_MAXK");
   if (ldv < ctx->n || ldg < k) return fail(LBFGSB_E_ARG, "qn_gram: ldv < n_local or ldg < k");
   return ctx->qn_vgram(mode, k, v, ldv, center, h_g, ldg);

@@ -23,7 +23,7 @@ namespace lbk {
 // CEN: the vectors are d_kk = v_kk - center, formed in fp64 in registers (no center: neither a load nor an address).
 // DD: K more sums d_kk'd_kk in the slots 2MC K + kk (the first column tile's launch of a quadratic form carries them).
 // GG: instead of them the K (K + 1) / 2 sums d_a'd_b, a <= b, row by row of the upper triangle from slot 2MC K on
-// (at K = 1 that is DD itself: launch_qn_wtg hands it to qn_wtd_kernel).
+// (at K = 1 that is DD itself: launch_qn_wtv hands it to qn_wtd_kernel).
 // The plain pass (qn_wtv_kernel) is the body with all three off.
 template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT, bool CEN, bool DD, bool GG = false>
 __device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
@@ -247,83 +247,45 @@ __global__ __launch_bounds__(BLOCK) void qn_diag_kernel(int64_t n, const T *__re
 }
 
 // ---------------------------------------------------------------- launches (dispatch: k_qn_common.hpp)
-int qn_mc(int ncols) { return ncols <= 5 ? 5 : (ncols <= 10 ? 10 : QN_TILE); }
-int qn_kmax(int mc) { return mc <= 10 ? 4 : 2; }
-
 hipError_t launch_qn_finalize(const Queue &q, const double *part, int nblocks, int nslots, double *res) {
+  if (nblocks == 0) return hipErrorInvalidValue;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(qn_finalize_kernel, dim3(nslots), dim3(BLOCK), 0, q.stream, part, nblocks, res);
   return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         QnVecs<T> v, bool vslot, double *part, double *res) {
-  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
-  // (two rows per lane only where operands + accumulators leave room for them: 2 mc k <= 20 sums)
-  bool vec2 = !vslot && 2 * mc * k <= 20;
+                         QnVecs<T> v, bool vslot, const T *center, QnCarry carry, double *part, double *res) {
+  if (!qn_block_ok(mc, k) || (vslot && (center || carry != QnCarry::None))) return hipErrorInvalidValue;
+  // (one vector: its Gram is its squared norm -- qn_wtd's kernel, no second instantiation of it)
+  const bool gg = carry == QnCarry::Gram && k >= 2, dd = carry != QnCarry::None && !gg;
+  // (two rows per lane only where operands + accumulators leave room for them: 2 mc k <= 20 sums.  At those shapes
+  //  the K squared norms and the center's V entries add 2 (K + V) <= 8 registers to the plain pass's operands and sums
+  //  -- 140 against 136 at the largest, mc = 10, k = 1: three waves per SIMD still; a Gram has them at 5 columns and
+  //  K = 2 only)
+  bool vec2 = !vslot && 2 * mc * k <= 20 && (!center || aligned_for(center, 2));
   for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
   int g = 0;
-  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(vslot, VS, QN_DISPATCH_BOOL(q.nt, NT, {
-    auto kern = qn_wtv_kernel<T, MC, K, V, CW, VS, NT>;
-    g = grid_for_w(q, n, V, (const void *)kern);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, v, part);
-  })))));
-  if (g == 0) return hipErrorInvalidValue;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_qn_finalize(q, part, g, 2 * mc * k, res);
-}
-
-template <typename T>
-hipError_t launch_qn_wtd(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         QnVecs<T> v, const T *center, bool dd, double *part, double *res) {
-  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
-  // (no center and no squared norm -- the later column tiles of an uncentred form: the plain pass itself)
-  if (!center && !dd) return launch_qn_wtv<T>(q, n, w, head, col, c0, mc, k, v, false, part, res);
-  // (rows per lane as qn_wtv: at the two-row shapes the K squared norms and the center's V entries add 2 (K + V) <= 8
-  //  registers to its operands and sums -- 140 against 136 at the largest, mc = 10, k = 1: three waves per SIMD still)
-  bool vec2 = 2 * mc * k <= 20 && (!center || aligned_for(center, 2));
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
-  int g = 0;
-  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT,
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
+    auto go = [&](auto kern, auto... cen) {
+      g = grid_for_w(q, n, V, (const void *)kern);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
+                         w.lmask, v, cen..., part);
+    };
+    if (!center && carry == QnCarry::None) {  // (the later column tiles of an uncentred form too: the plain pass)
+      QN_DISPATCH_BOOL(vslot, VS, go(qn_wtv_kernel<T, MC, K, V, CW, VS, NT>));
+    } else if (gg) {
+      if constexpr (K >= 2)
+        QN_DISPATCH_BOOL(center != nullptr, CEN, go(qn_wtg_kernel<T, MC, K, V, CW, NT, CEN>, center));
+    } else {
       QN_DISPATCH_BOOL(center != nullptr, CEN, QN_DISPATCH_BOOL(dd, DD, {
-    if constexpr (CEN || DD) {
-      auto kern = qn_wtd_kernel<T, MC, K, V, CW, NT, CEN, DD>;
-      g = grid_for_w(q, n, V, (const void *)kern);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                         w.lmask, v, center, part);
+        if constexpr (CEN || DD) go(qn_wtd_kernel<T, MC, K, V, CW, NT, CEN, DD>, center);
+      }));
     }
-  }))))));
-  if (g == 0) return hipErrorInvalidValue;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_qn_finalize(q, part, g, 2 * mc * k + (dd ? k : 0), res);
-}
-
-template <typename T>
-hipError_t launch_qn_wtg(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         QnVecs<T> v, const T *center, double *part, double *res) {
-  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
-  // (one vector: its Gram is its squared norm -- qn_wtd's own kernel, no second instantiation of it)
-  if (k == 1) return launch_qn_wtd<T>(q, n, w, head, col, c0, mc, k, v, center, true, part, res);
-  // (rows per lane as qn_wtd: two at 5 columns and K = 2 only)
-  bool vec2 = 2 * mc * k <= 20 && (!center || aligned_for(center, 2));
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
-  int g = 0;
-  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT,
-      QN_DISPATCH_BOOL(center != nullptr, CEN, {
-    if constexpr (K >= 2) {
-      auto kern = qn_wtg_kernel<T, MC, K, V, CW, NT, CEN>;
-      g = grid_for_w(q, n, V, (const void *)kern);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                         w.lmask, v, center, part);
-    }
-  })))));
-  if (g == 0) return hipErrorInvalidValue;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_qn_finalize(q, part, g, 2 * mc * k + k * (k + 1) / 2, res);
+  }))));
+  return launch_qn_finalize(q, part, g, 2 * mc * k + qn_carried(carry, k), res);
 }
 
 #define QN_DISPATCH_KAB(k, NAME, ...) \
@@ -354,9 +316,6 @@ hipError_t launch_qn_dtd(const Queue &q, int64_t n, QnVecs<T> a, int ka, QnVecs<
     g = grid_for_w(q, n, V2 ? 2 : 1, (const void *)kern);
     hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, a, b, center, part);
   })))));
-  if (g == 0) return hipErrorInvalidValue;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
   return launch_qn_finalize(q, part, g, ka * kb, res);
 }
 #undef QN_DISPATCH_KAB
@@ -364,15 +323,12 @@ hipError_t launch_qn_dtd(const Queue &q, int64_t n, QnVecs<T> a, int ka, QnVecs<
 template <typename T>
 hipError_t launch_qn_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                             const double *coef, double alpha, QnVecs<T> src, QnOuts<T> out) {
-  if (k < 1 || k > qn_kmax(mc) || k == 3) return hipErrorInvalidValue;
+  if (!qn_block_ok(mc, k)) return hipErrorInvalidValue;
   bool vec2 = 2 * mc * k <= 20;
   for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(src.p[kk], 2) && aligned_for((const T *)out.p[kk], 2);
   bool done = false;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
-    QnCoef<MC, K> cf{};
-    cf.alpha = alpha;
-    for (int kk = 0; kk < K; ++kk)
-      for (int j = 0; j < 2 * MC; ++j) cf.c[kk][j] = coef[(size_t)kk * 2 * MC + j];
+    const QnCoef<MC, K> cf = qn_coef_args<MC, K>(coef, alpha);
     auto kern = qn_expand_kernel<T, MC, K, V, CW, NT>;
     const int g = grid_for_w(q, n, V, (const void *)kern);
     hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
@@ -403,11 +359,7 @@ hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int 
 
 #define QN_INST(T)                                                                                                  \
   template hipError_t launch_qn_wtv<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
-                                       bool, double *, double *);                                                 \
-  template hipError_t launch_qn_wtd<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
-                                       const T *, bool, double *, double *);                                      \
-  template hipError_t launch_qn_wtg<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int, QnVecs<T>,   \
-                                       const T *, double *, double *);                                            \
+                                       bool, const T *, QnCarry, double *, double *);                             \
   template hipError_t launch_qn_dtd<T>(const Queue &, int64_t, QnVecs<T>, int, QnVecs<T>, int, const T *,       \
                                        double *, double *);                                                       \
   template hipError_t launch_qn_expand<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,          \

@@ -19,6 +19,16 @@ bool aligned_for(const T *p, int v) {
 }
 }  // namespace
 
+// the kernel argument of an expansion from the flat coefficients of its launch (qn_pack_coef: coef[kk * 2 MC + j])
+template <int MC, int K>
+QnCoef<MC, K> qn_coef_args(const double *coef, double alpha) {
+  QnCoef<MC, K> cf{};
+  cf.alpha = alpha;
+  for (int kk = 0; kk < K; ++kk)
+    for (int j = 0; j < 2 * MC; ++j) cf.c[kk][j] = coef[(size_t)kk * 2 * MC + j];
+  return cf;
+}
+
 #define QN_DISPATCH_MC(mc, ...)   \
   do {                            \
     if ((mc) == 5) {              \
@@ -40,7 +50,7 @@ bool aligned_for(const T *p, int v) {
     } else if ((k) == 2) {                    \
       constexpr int K = 2;                    \
       __VA_ARGS__;                            \
-    } else if constexpr (MC <= 10) {          \
+    } else if constexpr (qn_kmax(MC) >= 4) {  \
       constexpr int K = 4;                    \
       __VA_ARGS__;                            \
     }                                         \

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(BLOCK) void qn_draw_kernel(int64_t n, const T *__re
 namespace {
 // blocks of 1, 2 or 4 samples; a block of more than one sample is whole pairs
 bool draw_block_ok(int mc, int k, int64_t s0) {
-  return k >= 1 && k <= qn_kmax(mc) && k != 3 && s0 >= 0 && (k == 1 || (s0 & 1) == 0);
+  return qn_block_ok(mc, k) && s0 >= 0 && (k == 1 || (s0 & 1) == 0);
 }
 }  // namespace
 
@@ -176,9 +176,6 @@ hipError_t launch_qn_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int c
     hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
                        w.lmask, seed, row0, s0, part);
   }))));
-  if (g == 0) return hipErrorInvalidValue;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
   return launch_qn_finalize(q, part, g, 2 * mc * k + (zz ? k : 0), res);
 }
 
@@ -192,10 +189,7 @@ hipError_t launch_qn_draw(const Queue &q, int64_t n, WStore<T> w, int head, int 
   for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for((const T *)out.p[kk], 2);
   bool done = false;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
-    QnCoef<MC, K> cf{};
-    cf.alpha = alpha;
-    for (int kk = 0; kk < K; ++kk)
-      for (int j = 0; j < 2 * MC; ++j) cf.c[kk][j] = coef[(size_t)kk * 2 * MC + j];
+    const QnCoef<MC, K> cf = qn_coef_args<MC, K>(coef, alpha);
     auto kern = qn_draw_kernel<T, MC, K, V, CW, NT>;
     const int g = grid_for_w(q, n, V, (const void *)kern);
     hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,

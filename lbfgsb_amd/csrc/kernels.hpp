@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "qn_plan.hpp"     // QN_TILE, QN_KMAX, qn_mc, qn_kmax, QnCarry: the tiling of the curvature-model operators
 #include "res_layout.hpp"  // the slot layouts of the results, MAXM, maxc_for, RES_MAX, the split pass's sizes
 
 namespace lbk {
@@ -507,12 +508,8 @@ void launch_publish(Queue &q, const double *src, double *dst_host, int count, un
                     unsigned long long *flag_host);
 
 // ---- the curvature model as a device operator (k_qn.hip, solver_qn.inl) ----
-// Column tiles of at most QN_TILE pairs per launch of the W'V and expand passes (any number of pairs: one launch per
-// tile); blocks of K = 1, 2 or 4 vectors per launch (qn_kmax: K <= 4 up to 10 columns per tile, K <= 2 beyond).
-constexpr int QN_TILE = 16;
-constexpr int QN_KMAX = 4;
-int qn_mc(int ncols);  // column capacity (5, 10, QN_TILE) of a tile of ncols <= QN_TILE pairs
-int qn_kmax(int mc);
+// (qn_plan.hpp: the tiles of at most QN_TILE pairs and blocks of K = 1, 2 or 4 vectors that one launch of the W'V and
+//  expand passes takes, and where its sums land)
 template <typename T>
 struct QnVecs {  // the vectors of a block, each of n rows in natural order
   const T *p[QN_KMAX];
@@ -526,28 +523,23 @@ struct QnCoef {  // out_k = alpha src_k + S c[k][0..MC) + Y c[k][MC..2MC): <= 4 
   double c[K][2 * MC];
   double alpha;
 };
-// [S'v_k; Y'v_k] of the columns c0 .. c0 + mc - 1 (those >= col give zeros): partials into part ([slot][MAX_BLOCKS]),
-// then a fixed-order finalize into res[k * 2 mc + j] (j < mc: S, j >= mc: Y).  vslot: the vectors are columns of W
-// (row i read at its slot in the layout).  w.lmask may be set: the layout is read as it is.
+// [S'd_k; Y'd_k] of the columns c0 .. c0 + mc - 1 (those >= col give zeros), d_k = v_k - center (center may be NULL:
+// the vectors as they are): partials into part ([slot][MAX_BLOCKS]), then a fixed-order finalize into res[k * 2 mc + j]
+// (j < mc: S, j >= mc: Y).  carry: behind them, in res[2 mc k ...], the k sums d_k'd_k (Norms: the first tile's launch
+// of a quadratic form) or the k (k + 1) / 2 sums d_a'd_b, a <= b, row by row of the upper triangle (Gram: that of a
+// Gram matrix).  vslot: the vectors are columns of W (row i read at its slot in the layout; no center, nothing
+// carried).  w.lmask may be set: the layout is read as it is.  The kernel: qn_wtv_kernel with no center and nothing
+// carried, qn_wtg_kernel for a Gram of k >= 2 vectors, else qn_wtd_kernel (the Gram of one vector is its norm).
 template <typename T>
 hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         QnVecs<T> v, bool vslot, double *part, double *res);
-// The same for d_k = v_k - center (center may be NULL: the vectors as they are), vectors in natural order; dd: k more
-// sums d_k'd_k in res[2 mc k + kk] -- the W'V pass of a quadratic form, whose first tile carries the squared norms
-template <typename T>
-hipError_t launch_qn_wtd(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         QnVecs<T> v, const T *center, bool dd, double *part, double *res);
-// The same with the block's whole Gram along: k (k + 1) / 2 sums d_a'd_b, a <= b, row by row of the upper triangle in
-// res[2 mc k ...] -- the first tile's launch of a Gram matrix (lbfgsb_hip_qn_gram); k = 1 is launch_qn_wtd with dd
-template <typename T>
-hipError_t launch_qn_wtg(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                         QnVecs<T> v, const T *center, double *part, double *res);
+                         QnVecs<T> v, bool vslot, const T *center, QnCarry carry, double *part, double *res);
 // res[ia * kb + ib] = (a_ia - center)'(b_ib - center), ka, kb in {1, 2, 4} (center may be NULL): the entries of D'D
 // across two blocks of vectors, from the vectors alone
 template <typename T>
 hipError_t launch_qn_dtd(const Queue &q, int64_t n, QnVecs<T> a, int ka, QnVecs<T> b, int kb, const T *center,
                          double *part, double *res);
-// res[k] = the sum of slot k's nblocks partials, k < nslots, in a fixed order (launch_qn_wtv / launch_qn_wtz end so)
+// res[k] = the sum of slot k's nblocks partials, k < nslots, in a fixed order: how launch_qn_wtv / wtz / dtd end, with
+// the grid of the pass they launched (0: the dispatch found no kernel) and after asking for its launch error
 hipError_t launch_qn_finalize(const Queue &q, const double *part, int nblocks, int nslots, double *res);
 // out_k = alpha src_k + [S, Y](:, tile) coef[k * 2 mc ...] (src_k may be out_k: the second and later tiles)
 template <typename T>

@@ -1,0 +1,98 @@
+// qn_plan.hpp -- the tiling plan of the curvature-model operators (solver_qn.inl, k_qn.hip, k_qn_draw.hip; DESIGN.md
+// section 10): which launches a pass over W = [S, Y] is made of and where each of their sums lands.  Host-only integer
+// bookkeeping, no HIP and nothing of Solver: tests/qn_plan_check.cpp walks it exhaustively on the CPU.
+//
+// The rule, stated here and nowhere else: the columns of W go in tiles of at most QN_TILE pairs from column 0, a tile
+// of ncols pairs has the capacity qn_mc(ncols) = 5 / 10 / 16, and the (at most QN_KMAX) vectors of a block go through
+// a tile in pieces of 4 / 2 / 1 (qn_piece_k: 3 = 2 + 1, at most 2 on a tile of 16).  One piece is one launch.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <vector>
+
+namespace lbk {
+
+constexpr int QN_TILE = 16;
+constexpr int QN_KMAX = 4;
+// column capacity of a tile of ncols <= QN_TILE pairs
+constexpr int qn_mc(int ncols) { return ncols <= 5 ? 5 : (ncols <= 10 ? 10 : QN_TILE); }
+// the widest block of vectors a launch on a tile of capacity mc takes
+constexpr int qn_kmax(int mc) { return mc <= 10 ? 4 : 2; }
+// the vectors that the next launch takes of `left` remaining ones
+constexpr int qn_piece_k(int left, int mc) {
+  const int k = left < qn_kmax(mc) ? left : qn_kmax(mc);
+  return k == 3 ? 2 : k;
+}
+// a block that a launch accepts: what qn_piece_k can return
+constexpr bool qn_block_ok(int mc, int k) { return k >= 1 && qn_piece_k(k, mc) == k; }
+
+// what the launches of the first tile carry behind their W'V sums: nothing, the k squared norms of the piece's
+// vectors (quadratic forms, draw densities), or the k (k + 1) / 2 sums d_a'd_b, a <= b, row by row (Gram matrices)
+enum class QnCarry { None, Norms, Gram };
+constexpr int qn_carried(QnCarry c, int k) {
+  return c == QnCarry::Gram ? k * (k + 1) / 2 : c == QnCarry::Norms ? k : 0;
+}
+
+struct QnPiece {  // one launch: the vectors k0 .. k0 + k - 1 on the column tile at c0, its sums from slot off on
+  int c0, mc, k0, k, off;
+  QnCarry carry;  // (None on every tile but the first)
+  constexpr int slots() const { return 2 * mc * k + qn_carried(carry, k); }
+};
+struct QnPlan {
+  int col, kc;
+  std::vector<QnPiece> pieces;  // tile by tile, within a tile by vector
+  int total;                    // slots of all pieces
+};
+// the slots a plan can need: 2 (col + QN_TILE) kc sums and the widest carry, for col <= max_m and kc <= QN_KMAX
+constexpr int qn_res(int max_m) { return 2 * (max_m + QN_TILE) * QN_KMAX + qn_carried(QnCarry::Gram, QN_KMAX); }
+
+// The pieces of one pass over the col stored pairs for a block of kc <= QN_KMAX vectors.  With no pair there is no
+// tile, unless something is carried or the pass writes an output (expand: the second pass of qn_apply and the draws):
+// then one empty tile, whose launches read the zero line and nothing of W.
+inline QnPlan qn_plan(int col, int kc, QnCarry carry, bool expand = false) {
+  QnPlan pl{col, kc, {}, 0};
+  for (int c0 = 0; c0 < std::max(col, carry != QnCarry::None || expand ? 1 : 0); c0 += QN_TILE) {
+    const int mc = qn_mc(std::max(1, std::min(QN_TILE, col - c0)));
+    for (int k0 = 0; k0 < kc;) {
+      const QnPiece p{c0, mc, k0, qn_piece_k(kc - k0, mc), pl.total, c0 == 0 ? carry : QnCarry::None};
+      pl.pieces.push_back(p);
+      pl.total += p.slots();
+      k0 += p.k;
+    }
+  }
+  return pl;
+}
+
+// res (the fetched slots) -> out[k * 2 col + i] = S(:, i)'v_k for i < col, Y(:, i - col)'v_k beyond
+inline void qn_scatter_sums(const QnPlan &pl, const double *res, double *out) {
+  for (const QnPiece &p : pl.pieces)
+    for (int kk = 0; kk < p.k; ++kk) {
+      double *o = out + (size_t)(p.k0 + kk) * 2 * pl.col;
+      const double *r = res + (size_t)p.off + kk * 2 * p.mc;
+      for (int j = 0; j < p.mc && p.c0 + j < pl.col; ++j) o[p.c0 + j] = r[j], o[pl.col + p.c0 + j] = r[p.mc + j];
+    }
+}
+// the carried slots -> dst[k] (Norms), or dst[a + b QN_KMAX] for a <= b of one piece (Gram: entries across two pieces
+// are left as they are)
+inline void qn_scatter_carry(const QnPlan &pl, const double *res, double *dst) {
+  for (const QnPiece &p : pl.pieces) {
+    const double *r = res + (size_t)p.off + 2 * p.mc * p.k;
+    if (p.carry == QnCarry::Norms)
+      for (int kk = 0; kk < p.k; ++kk) dst[p.k0 + kk] = r[kk];
+    if (p.carry == QnCarry::Gram)
+      for (int a = 0; a < p.k; ++a)
+        for (int b = a; b < p.k; ++b) dst[(p.k0 + a) + (size_t)(p.k0 + b) * QN_KMAX] = *r++;
+  }
+}
+// the other way, for an expansion: cf[k * 2 col + i] -> the 2 mc k coefficients of one piece's launch,
+// coef[kk * 2 mc + j] for S(:, c0 + j) and coef[kk * 2 mc + mc + j] for Y(:, c0 + j), zero for the columns >= col
+inline void qn_pack_coef(const QnPiece &p, int col, const double *cf, double *coef) {
+  std::fill(coef, coef + 2 * p.mc * p.k, 0.0);
+  for (int kk = 0; kk < p.k; ++kk) {
+    const double *c = cf + (size_t)(p.k0 + kk) * 2 * col;
+    double *o = coef + (size_t)kk * 2 * p.mc;
+    for (int j = 0; j < p.mc && p.c0 + j < col; ++j) o[j] = c[p.c0 + j], o[p.mc + j] = c[col + p.c0 + j];
+  }
+}
+
+}  // namespace lbk

@@ -4,6 +4,9 @@
 // symmetric square roots, log-determinants and draws (lbfgsb_hip_qn_logdet, lbfgsb_hip_qn_draw; k_qn_draw.hip), and
 // quadratic forms and Gaussian log-densities (lbfgsb_hip_qn_quad, qn_logpdf, qn_draw_logpdf),
 // and Gram matrices on blocks of vectors (lbfgsb_hip_qn_gram; section 10d).
+// Which launches a pass over W is made of and where their sums land is decided in one place, qn_plan.hpp (host-only,
+// walked on the CPU by tests/qn_plan_check.cpp): every W'V pass here goes through qn_sums_by on a plan, every
+// expansion through qn_expand_by, and a new operator hooks in with a plan and a launch of its own.
 //
 // The entries read the pairs of the last return (or import) and nothing else of the iteration's state changes:
 // W is read in the layout it is in (Wc(), never W()), the sums go through buffers of their own (never q.d_part /
@@ -28,10 +31,7 @@
     double *h_n = nullptr;      // pinned staging of a packed N
     std::vector<double> h_res, h_all;
   } qn;
-  // sums of one vector block: 2 (col + QN_TILE) per vector, and its squared norms (quadratic forms, draw densities)
-  // or the upper triangle of its Gram (Gram matrices)
-  static constexpr int QN_RES =
-      2 * (LBFGSB_MAX_M + lbk::QN_TILE) * lbk::QN_KMAX + lbk::QN_KMAX * (lbk::QN_KMAX + 1) / 2;
+  static constexpr int QN_RES = lbk::qn_res(LBFGSB_MAX_M);                          // the sums of one vector block
   static constexpr int QN_NP = 64 * 65 / 2;                                         // packed N at 32 pairs
 
   // save_locals: what the entries will read until the next return
@@ -109,106 +109,54 @@
     if (e == hipSuccess) return 0;
     return fail(LBFGSB_E_NOGPU, std::string("qn: launch of ") + what + " failed: " + hipGetErrorString(e));
   }
-  struct QnPiece {  // one launch of a W'V pass: the vectors k0 .. k0 + k - 1 on the column tile at c0, sums at off
-    int c0, mc, k0, k, off;
-    bool sq;  // the launch carries the k squared norms too, behind its 2 mc k sums (the first tile, when asked for)
-              // -- of a Gram matrix the k (k + 1) / 2 sums d_a'd_b of the piece, a <= b, row by row
-  };
-  // the vectors of a block that the next launch on a tile of capacity mc takes: 4 / 2 / 1, 3 -> 2 + 1
-  static int qn_piece_k(int left, int mc) {
-    const int k = std::min(left, lbk::qn_kmax(mc));
-    return k == 3 ? 2 : k;
+  using QnCarry = lbk::QnCarry;
+  double qn_alpha(bool inv) const { return inv ? 1.0 / qn.theta : qn.theta; }
+  // One W'V pass by a plan of qn.col pairs (qn_plan.hpp): a launch per piece, one fetch of all their sums (all ranks
+  // reduced), then [S'v_k; Y'v_k] -> out[k * 2 col + i] (i < col: S, else Y) and what the first tile's launches
+  // carried -> carried (qn_scatter_carry; NULL with QnCarry::None).  With no stored pair a carry goes by launches on
+  // an empty tile, which read the zero line and nothing of W.
+  template <typename L>
+  int qn_sums_by(const lbk::QnPlan &pl, double *out, double *carried, L &&launch) {
+    // (<= qn_res(LBFGSB_MAX_M) for every col <= LBFGSB_MAX_M; checked before anything is written)
+    if (pl.total > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");
+    for (const lbk::QnPiece &p : pl.pieces) CHK(launch(p));
+    CHK(qn_reduce(pl.total));
+    lbk::qn_scatter_sums(pl, qn.h_res.data(), out);
+    lbk::qn_scatter_carry(pl, qn.h_res.data(), carried);
+    return 0;
   }
-  // [S'v_k; Y'v_k] for kc <= QN_KMAX vectors -> out[k * 2 col + i] (i < col: S, else Y), all ranks reduced
-  int qn_sums(const T *const *v, int kc, bool vslot, double *out) {
+  // the pass for d_k = v_k - center (center may be NULL: the vectors as they are).  vslot: the vectors are columns of
+  // W, read at their slots in its layout (no center, nothing carried)
+  int qn_sums(const lbk::QnPlan &pl, const T *const *v, bool vslot, const T *center, double *out, double *carried) {
     const lbk::WStore<T> w = Wc();
-    return qn_sums_by(kc, out, nullptr, [&](const QnPiece &p) {
+    return qn_sums_by(pl, out, carried, [&](const lbk::QnPiece &p) {
       lbk::QnVecs<T> vv{};
       for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
-      return qn_launched(lbk::launch_qn_wtv<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, vslot, qn.d_part,
-                                               qn.d_res + p.off),
+      return qn_launched(lbk::launch_qn_wtv<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, vslot, center, p.carry,
+                                               qn.d_part, qn.d_res + p.off),
                          "qn_wtv");
     });
   }
-  // the same with the vectors generated: the samples s0 .. s0 + kc - 1 of seed (s0 even unless kc = 1)
-  // zz (kc values, or NULL): z_k'z_k over all rows as well -- the other sums are the same bits either way
-  int qn_sums_z(uint64_t seed, int64_t s0, int kc, double *out, double *zz = nullptr) {
+  // the same with the vectors generated: the samples s0 .. s0 + kc - 1 of seed (s0 even unless kc = 1); the W'z sums
+  // are the same bits whether z_k'z_k is carried or not
+  int qn_sums_z(const lbk::QnPlan &pl, uint64_t seed, int64_t s0, double *out, double *zz) {
     const lbk::WStore<T> w = Wc();
-    return qn_sums_by(kc, out, zz, [&](const QnPiece &p) {
+    return qn_sums_by(pl, out, zz, [&](const lbk::QnPiece &p) {
       return qn_launched(lbk::launch_qn_wtz<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, seed, row0, s0 + p.k0,
-                                               p.sq, qn.d_part, qn.d_res + p.off),
+                                               p.carry == QnCarry::Norms, qn.d_part, qn.d_res + p.off),
                          "qn_wtz");
     });
   }
-  // the sums of d_k = v_k - center (center may be NULL) and dd[k] = d_k'd_k
-  int qn_sums_d(const T *const *v, int kc, const T *center, double *out, double *dd) {
-    const lbk::WStore<T> w = Wc();
-    return qn_sums_by(kc, out, dd, [&](const QnPiece &p) {
-      lbk::QnVecs<T> vv{};
-      for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
-      return qn_launched(lbk::launch_qn_wtd<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, center, p.sq,
-                                               qn.d_part, qn.d_res + p.off),
-                         "qn_wtd");
-    });
-  }
-  // the same with the Gram of every piece of the first tile: gr[a + b QN_KMAX] = d_a'd_b for a <= b of one piece
-  // (the squared norms among them); entries across two pieces are left as they are (qn_sums_dd)
-  int qn_sums_g(const T *const *v, int kc, const T *center, double *out, double *gr) {
-    const lbk::WStore<T> w = Wc();
-    return qn_sums_by(
-        kc, out, gr,
-        [&](const QnPiece &p) {
-          lbk::QnVecs<T> vv{};
-          for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
-          if (p.sq)
-            return qn_launched(lbk::launch_qn_wtg<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, center, qn.d_part,
-                                                     qn.d_res + p.off),
-                               "qn_wtg");
-          return qn_launched(lbk::launch_qn_wtd<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, center, false,
-                                                   qn.d_part, qn.d_res + p.off),
-                             "qn_wtd");
-        },
-        true);
-  }
-  // sq (kc values) or NULL: the vectors' squared norms, carried by the launches of the first column tile -- with no
-  // stored pair by launches on an empty tile, which read the zero line and nothing of W.  gram: sq is a QN_KMAX x
-  // QN_KMAX matrix instead and the first tile's launches carry the upper triangle of each piece's Gram
+  // The second pass of qn_apply and the draws: out_k (+)= [S, Y] cf_k tile by tile (with no pair one empty tile, which
+  // writes alpha v or the plain draw).  launch(piece, coef): one launch with the piece's 2 mc k packed coefficients
   template <typename L>
-  int qn_sums_by(int kc, double *out, double *sq, L &&launch, bool gram = false) {
-    const int col = qn.col;
-    using Piece = QnPiece;
-    std::vector<Piece> pieces;
-    int off = 0;
-    for (int c0 = 0; c0 < std::max(col, sq ? 1 : 0); c0 += lbk::QN_TILE) {
-      const int mc = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col - c0)));
-      for (int k0 = 0; k0 < kc;) {  // blocks of 4 / 2 / 1 vectors the tile's kernels take
-        const int k = qn_piece_k(kc - k0, mc);
-        const bool carry = sq && c0 == 0;
-        pieces.push_back(Piece{c0, mc, k0, k, off, carry});
-        off += 2 * mc * k + (carry ? (gram ? k * (k + 1) / 2 : k) : 0);
-        k0 += k;
-      }
+  int qn_expand_by(int kc, const double *cf, L &&launch) {
+    const lbk::QnPlan pl = lbk::qn_plan(qn.col, kc, QnCarry::None, true);
+    for (const lbk::QnPiece &p : pl.pieces) {
+      double coef[2 * lbk::QN_TILE * lbk::QN_KMAX];
+      lbk::qn_pack_coef(p, qn.col, cf, coef);
+      CHK(launch(p, coef));
     }
-    // (<= 2 (col + QN_TILE) kc + kc (kc + 1) / 2 <= QN_RES for every col <= LBFGSB_MAX_M; checked before anything is
-    //  written)
-    if (off > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");
-    for (const Piece &p : pieces) CHK(launch(p));
-    CHK(qn_reduce(off));
-    for (const Piece &p : pieces)
-      for (int kk = 0; kk < p.k; ++kk) {
-        for (int j = 0; j < p.mc && p.c0 + j < col; ++j) {
-          double *o = out + (size_t)(p.k0 + kk) * 2 * col;
-          o[p.c0 + j] = qn.h_res[(size_t)p.off + kk * 2 * p.mc + j];
-          o[col + p.c0 + j] = qn.h_res[(size_t)p.off + kk * 2 * p.mc + p.mc + j];
-        }
-        if (p.sq && !gram) sq[p.k0 + kk] = qn.h_res[(size_t)p.off + 2 * p.mc * p.k + kk];
-      }
-    for (const Piece &p : pieces)
-      if (p.sq && gram) {
-        const double *r = qn.h_res.data() + (size_t)p.off + 2 * p.mc * p.k;
-        for (int a = 0; a < p.k; ++a)
-          for (int b = a; b < p.k; ++b) sq[(p.k0 + a) + (size_t)(p.k0 + b) * lbk::QN_KMAX] = *r++;
-      }
     return 0;
   }
   // S'Y and Y'Y over all rows, once per pair generation (the vectors of the W'V pass are the columns of Y)
@@ -221,7 +169,7 @@
       const int kc = std::min(lbk::QN_KMAX, col - k0);
       const T *v[lbk::QN_KMAX];
       for (int kk = 0; kk < kc; ++kk) v[kk] = wy + (int64_t)((qn.head - 1 + k0 + kk) % m) * ld;
-      CHK(qn_sums(v, kc, true, sums.data()));
+      CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::None), v, true, nullptr, sums.data(), nullptr));
       for (int kk = 0; kk < kc; ++kk)
         for (int i = 0; i < col; ++i) {
           qn.sty[i + (size_t)(k0 + kk) * col] = sums[(size_t)kk * 2 * col + i];
@@ -248,6 +196,12 @@
     const int info = lbh::qn_coef_b(m, sy.data(), wt.data(), col, qn.theta, stv, ytv, cs, cy);
     return info ? fail(LBFGSB_E_STATE, "qn: the middle matrix is singular (wt)") : 0;
   }
+  // that as the map (S'v, Y'v, cs, cy) which lbh::qn_nmat and lbh::qn_gram_combine take
+  auto qn_coef_map(bool inv) {
+    return [this, inv, dg = qn_dg()](const double *stv, const double *ytv, double *cs, double *cy) {
+      return qn_coef(inv, dg.data(), stv, ytv, cs, cy);
+    };
+  }
 
   // C of A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' and the log-det sum of B (inv = false) or H, once per pair
   // generation (host_dense.hpp, qn_root): G = [S, Y]'[S, Y] from ss and the Gram, N as qn_diag forms it
@@ -257,14 +211,8 @@
     if (col == 0) return 0;
     CHK(qn_gram());
     if (qn.root_gen[md] == qn.gen) return 0;
-    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
-    const std::vector<double> dg = qn_dg();
     std::vector<double> nm((size_t)d * d), g((size_t)d * d), work((size_t)6 * d * d + d);
-    const int info = lbh::qn_nmat(
-        col, [&](const double *stv, const double *ytv, double *cs, double *cy) {
-          return qn_coef(inv, dg.data(), stv, ytv, cs, cy);
-        },
-        nm.data());
+    const int info = lbh::qn_nmat(col, qn_coef_map(inv), nm.data());
     if (info) return info;
     for (int j = 0; j < col; ++j)
       for (int i = 0; i < col; ++i) {
@@ -280,7 +228,7 @@
     qn.root_c[md].assign((size_t)d * d, 0.0);
     qn.root_gen[md] = -1;
     const int rc =
-        lbh::qn_root(d, alpha, g.data(), nm.data(), qn.root_c[md].data(), &qn.root_logsum[md], work.data());
+        lbh::qn_root(d, qn_alpha(inv), g.data(), nm.data(), qn.root_c[md].data(), &qn.root_logsum[md], work.data());
     if (rc == -2) return fail(LBFGSB_E_STATE, "qn: the model is not positive definite");
     if (rc) return fail(LBFGSB_E_STATE, "qn: the eigensolver of the root did not converge");
     qn.root_gen[md] = qn.gen;
@@ -299,8 +247,7 @@
 
   // log det A over all rows (after qn_root_coef(inv))
   double qn_logdet_of(bool inv) const {
-    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
-    return (double)nglob * std::log(alpha) + (qn.col > 0 ? qn.root_logsum[inv ? 1 : 0] : 0.0);
+    return (double)nglob * std::log(qn_alpha(inv)) + (qn.col > 0 ? qn.root_logsum[inv ? 1 : 0] : 0.0);
   }
   int qn_logdet(int mode, double *h_logdet) override {
     CHK(qn_ready());
@@ -329,7 +276,7 @@
     const int col = qn.col;
     const double lconst = h_logp ? qn_log_norm(inv, scale) : 0.0;
     double zz[lbk::QN_KMAX];
-    const double ra = std::sqrt(inv ? 1.0 / qn.theta : qn.theta);
+    const double ra = std::sqrt(qn_alpha(inv));
     const lbk::WStore<T> w = Wc();
     const T *mean = (const T *)mean_;
     T *out = (T *)out_;
@@ -338,32 +285,18 @@
       const int64_t s0 = first + k0;
       const int kc = (s0 & 1) ? 1 : (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
       if (col > 0 || h_logp) {
-        CHK(qn_sums_z(seed, s0, kc, sums.data(), h_logp ? zz : nullptr));
+        CHK(qn_sums_z(lbk::qn_plan(col, kc, h_logp ? QnCarry::Norms : QnCarry::None), seed, s0, sums.data(), zz));
         for (int kk = 0; kk < kc && col > 0; ++kk)
           qn_root_map(inv, scale, sums.data() + (size_t)kk * 2 * col, cf.data() + (size_t)kk * 2 * col);
         for (int kk = 0; kk < kc && h_logp; ++kk) h_logp[k0 + kk] = -0.5 * (lconst + zz[kk]);
       }
-      for (int c0 = 0; c0 < std::max(col, 1); c0 += lbk::QN_TILE) {
-        const int mc = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col - c0)));
-        for (int j0 = 0; j0 < kc;) {
-          int kb = std::min(kc - j0, lbk::qn_kmax(mc));
-          if (kb == 3) kb = 2;
-          double coef[2 * lbk::QN_TILE * lbk::QN_KMAX] = {};
-          lbk::QnOuts<T> dst{};
-          for (int kk = 0; kk < kb; ++kk) {
-            const double *c = cf.data() + (size_t)(j0 + kk) * 2 * col;
-            for (int j = 0; j < mc && c0 + j < col; ++j) {
-              coef[(size_t)kk * 2 * mc + j] = c[c0 + j];
-              coef[(size_t)kk * 2 * mc + mc + j] = c[col + c0 + j];
-            }
-            dst.p[kk] = out + (k0 + j0 + kk) * ldo;
-          }
-          CHK(qn_launched(lbk::launch_qn_draw<T>(q, n, w, qn.head, col, c0, mc, kb, coef, scale * ra, seed, row0,
-                                                 s0 + j0, c0 == 0, mean, dst),
-                          "qn_draw"));
-          j0 += kb;
-        }
-      }
+      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
+        lbk::QnOuts<T> dst{};
+        for (int kk = 0; kk < p.k; ++kk) dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
+        return qn_launched(lbk::launch_qn_draw<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef, scale * ra, seed,
+                                                  row0, s0 + p.k0, p.c0 == 0, mean, dst),
+                           "qn_draw");
+      }));
       k0 += kc;
     }
     return qn_finish();
@@ -378,7 +311,7 @@
   int qn_quad_by(bool inv, int64_t k, const T *v, int64_t ldv, const T *center, double *h_q) {
     const int col = qn.col;
     if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
-    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
+    const double alpha = qn_alpha(inv);
     const std::vector<double> dg = qn_dg();
     std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), c((size_t)2 * std::max(col, 1));
     double dd[lbk::QN_KMAX];
@@ -386,7 +319,7 @@
       const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
       const T *vp[lbk::QN_KMAX];
       for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (k0 + kk) * ldv;
-      CHK(qn_sums_d(vp, kc, center, sums.data(), dd));
+      CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::Norms), vp, false, center, sums.data(), dd));
       for (int kk = 0; kk < kc; ++kk) {
         const double *sv = sums.data() + (size_t)kk * 2 * col;
         double t = 0.0;  // p'(N p), S part then Y part, ascending
@@ -438,34 +371,25 @@
     const bool inv = mode == LBFGSB_QN_H;
     const int col = qn.col, k = (int)k_, d = 2 * col;
     if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
-    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
     const T *v = (const T *)v_, *center = (const T *)center_;
     std::vector<double> p((size_t)std::max(d, 1) * k), dtd((size_t)k * k, 0.0);
     std::vector<std::pair<int, int>> pc;
-    const int mc0 = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col)));
     for (int k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
-      const int kc = std::min(lbk::QN_KMAX, k - k0);
+      const lbk::QnPlan pl = lbk::qn_plan(col, std::min(lbk::QN_KMAX, k - k0), QnCarry::Gram);
       const T *vp[lbk::QN_KMAX];
-      for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (int64_t)(k0 + kk) * ldv;
+      for (int kk = 0; kk < pl.kc; ++kk) vp[kk] = v + (int64_t)(k0 + kk) * ldv;
       double gr[lbk::QN_KMAX * lbk::QN_KMAX] = {};
-      CHK(qn_sums_g(vp, kc, center, p.data() + (size_t)k0 * d, gr));
-      for (int j0 = 0; j0 < kc;) {  // the pieces qn_sums_by has formed on the first tile
-        const int kb = qn_piece_k(kc - j0, mc0);
-        pc.emplace_back(k0 + j0, kb);
-        for (int a = 0; a < kb; ++a)
-          for (int b = a; b < kb; ++b)
-            dtd[(k0 + j0 + a) + (size_t)(k0 + j0 + b) * k] = gr[(j0 + a) + (size_t)(j0 + b) * lbk::QN_KMAX];
-        j0 += kb;
+      CHK(qn_sums(pl, vp, false, center, p.data() + (size_t)k0 * d, gr));
+      for (const lbk::QnPiece &pp : pl.pieces) {  // the pieces of the first tile: they carried their Grams
+        if (pp.carry != QnCarry::Gram) continue;
+        pc.emplace_back(k0 + pp.k0, pp.k);
+        for (int a = pp.k0; a < pp.k0 + pp.k; ++a)
+          for (int b = a; b < pp.k0 + pp.k; ++b)
+            dtd[(k0 + a) + (size_t)(k0 + b) * k] = gr[a + (size_t)b * lbk::QN_KMAX];
       }
     }
     CHK(qn_sums_dd(v, ldv, center, pc, dtd.data(), k));
-    const std::vector<double> dg = qn_dg();
-    return lbh::qn_gram_combine(
-        col, k, alpha, p.data(), dtd.data(), k,
-        [&](const double *stv, const double *ytv, double *cs, double *cy) {
-          return qn_coef(inv, dg.data(), stv, ytv, cs, cy);
-        },
-        h_g, ldg);
+    return lbh::qn_gram_combine(col, k, qn_alpha(inv), p.data(), dtd.data(), k, qn_coef_map(inv), h_g, ldg);
   }
   int qn_quad(int mode, int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) override {
     CHK(qn_ready());
@@ -490,7 +414,7 @@
     const int col = qn.col;
     if (root) CHK(qn_root_coef(inv));
     if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
-    const double alpha = root ? std::sqrt(inv ? 1.0 / qn.theta : qn.theta) : inv ? 1.0 / qn.theta : qn.theta;
+    const double alpha = root ? std::sqrt(qn_alpha(inv)) : qn_alpha(inv);
     const std::vector<double> dg = qn_dg();
     const lbk::WStore<T> w = Wc();
     const T *v = (const T *)v_;
@@ -501,7 +425,7 @@
       const T *vp[lbk::QN_KMAX];
       for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (k0 + kk) * ldv;
       if (col > 0) {
-        CHK(qn_sums(vp, kc, false, sums.data()));
+        CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::None), vp, false, nullptr, sums.data(), nullptr));
         for (int kk = 0; kk < kc; ++kk) {
           const double *sv = sums.data() + (size_t)kk * 2 * col;
           double *c = cf.data() + (size_t)kk * 2 * col;
@@ -510,29 +434,17 @@
         }
       }
       // out = alpha v + [S, Y] (cs; cy), one launch per column tile and block of vectors (col = 0: alpha v)
-      for (int c0 = 0; c0 < std::max(col, 1); c0 += lbk::QN_TILE) {
-        const int mc = lbk::qn_mc(std::max(1, std::min(lbk::QN_TILE, col - c0)));
-        for (int j0 = 0; j0 < kc;) {
-          int kb = std::min(kc - j0, lbk::qn_kmax(mc));
-          if (kb == 3) kb = 2;
-          double coef[2 * lbk::QN_TILE * lbk::QN_KMAX] = {};
-          lbk::QnVecs<T> src{};
-          lbk::QnOuts<T> dst{};
-          for (int kk = 0; kk < kb; ++kk) {
-            const double *c = cf.data() + (size_t)(j0 + kk) * 2 * col;
-            for (int j = 0; j < mc && c0 + j < col; ++j) {
-              coef[(size_t)kk * 2 * mc + j] = c[c0 + j];
-              coef[(size_t)kk * 2 * mc + mc + j] = c[col + c0 + j];
-            }
-            dst.p[kk] = out + (k0 + j0 + kk) * ldo;
-            src.p[kk] = c0 == 0 ? vp[j0 + kk] : dst.p[kk];
-          }
-          CHK(qn_launched(lbk::launch_qn_expand<T>(q, n, w, qn.head, col, c0, mc, kb, coef, c0 == 0 ? alpha : 1.0,
-                                                   src, dst),
-                          "qn_expand"));
-          j0 += kb;
+      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
+        lbk::QnVecs<T> src{};
+        lbk::QnOuts<T> dst{};
+        for (int kk = 0; kk < p.k; ++kk) {
+          dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
+          src.p[kk] = p.c0 == 0 ? vp[p.k0 + kk] : dst.p[kk];
         }
-      }
+        return qn_launched(lbk::launch_qn_expand<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef,
+                                                    p.c0 == 0 ? alpha : 1.0, src, dst),
+                           "qn_expand");
+      }));
     }
     return qn_finish();
   }
@@ -543,17 +455,11 @@
     const int col = qn.col;
     if (col > lbk::MAXM) return fail(LBFGSB_E_ARG, "qn_diag: more than 32 stored pairs");
     if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
-    const double alpha = inv ? 1.0 / qn.theta : qn.theta;
     const int md = inv ? 1 : 0;
     if (qn.n_gen[md] != qn.gen || col == 0) {
       std::vector<double> nm((size_t)4 * col * col + 1);
       if (col > 0) {
-        const std::vector<double> dg = qn_dg();
-        const int info = lbh::qn_nmat(
-            col, [&](const double *stv, const double *ytv, double *cs, double *cy) {
-              return qn_coef(inv, dg.data(), stv, ytv, cs, cy);
-            },
-            nm.data());
+        const int info = lbh::qn_nmat(col, qn_coef_map(inv), nm.data());
         if (info) return info;
       }
       HIPCHK(hipStreamSynchronize(stream));  // (the staging buffer may still feed an earlier copy)
@@ -561,7 +467,8 @@
       HIPCHK(hipMemcpyAsync(qn.d_n[md], qn.h_n, (size_t)QN_NP * sizeof(double), hipMemcpyHostToDevice, stream));
       qn.n_gen[md] = qn.gen;
     }
-    CHK(qn_launched(lbk::launch_qn_diag<T>(q, n, Wc(), qn.head, col, qn.d_n[md], alpha, (T *)out_), "qn_diag"));
+    CHK(qn_launched(lbk::launch_qn_diag<T>(q, n, Wc(), qn.head, col, qn.d_n[md], qn_alpha(inv), (T *)out_),
+                    "qn_diag"));
     return qn_finish();
   }
   int qn_finish() {
