@@ -123,7 +123,7 @@ int lbfgsb_hip_wait_stream(lbfgsb_hip_ctx *ctx, void *producer_stream) {
   if (!ctx) return fail(LBFGSB_E_ARG, "ctx == NULL");
   if ((hipStream_t)producer_stream == ctx->q.stream) return 0;
   HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->order_ev) HIPCHK(hipEventCreateWithFlags(&ctx->order_ev, hipEventDisableTiming));
+  if (!ctx->order_ev) HIPCHK(ctx->own.event(&ctx->order_ev, hipEventDisableTiming));
   HIPCHK(hipEventRecord(ctx->order_ev, (hipStream_t)producer_stream));
   HIPCHK(hipStreamWaitEvent(ctx->q.stream, ctx->order_ev, 0));
   return 0;
@@ -132,7 +132,7 @@ int lbfgsb_hip_wait_stream(lbfgsb_hip_ctx *ctx, void *producer_stream) {
 int lbfgsb_hip_return_event(lbfgsb_hip_ctx *ctx, void *consumer_stream, int make_wait, void **event_out) {
   if (!ctx) return fail(LBFGSB_E_ARG, "ctx == NULL");
   HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->return_ev) HIPCHK(hipEventCreateWithFlags(&ctx->return_ev, hipEventDisableTiming));
+  if (!ctx->return_ev) HIPCHK(ctx->own.event(&ctx->return_ev, hipEventDisableTiming));
   HIPCHK(hipEventRecord(ctx->return_ev, ctx->q.stream));
   if (make_wait && (hipStream_t)consumer_stream != ctx->q.stream)
     HIPCHK(hipStreamWaitEvent((hipStream_t)consumer_stream, ctx->return_ev, 0));
@@ -385,9 +385,10 @@ int lbfgsb_hip_wtv_time(lbfgsb_hip_ctx *ctx, const void *v, int col, int head, i
                         double *h_ms_per_launch) {
   if (!ctx || !v || !h_ms_per_launch || reps < 1) return fail(LBFGSB_E_ARG, "wtv_time: bad arguments");
   HIPCHK(hipSetDevice(ctx->device));
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  GpuOwner tmp;  // (gives both back on every way out)
+  HIPCHK(tmp.event(&e0));
+  HIPCHK(tmp.event(&e1));
   for (int k = 0; k < 3; ++k) CHK(ctx->k_wtv(v, col, head, nullptr, true));
   HIPCHK(hipEventRecord(e0, ctx->q.stream));
   for (int k = 0; k < reps; ++k) CHK(ctx->k_wtv(v, col, head, nullptr, true));
@@ -395,8 +396,6 @@ int lbfgsb_hip_wtv_time(lbfgsb_hip_ctx *ctx, const void *v, int col, int head, i
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *h_ms_per_launch = (double)ms / reps;
   return 0;
 }
@@ -404,9 +403,10 @@ int lbfgsb_hip_kernel_time(lbfgsb_hip_ctx *ctx, int which, const void *x, const 
                            int head, int reps, double *h_ms_per_launch) {
   if (!ctx || !x || !g || !h_ms_per_launch || reps < 1) return fail(LBFGSB_E_ARG, "kernel_time: bad arguments");
   HIPCHK(hipSetDevice(ctx->device));
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  GpuOwner tmp;  // (gives both back on every way out)
+  HIPCHK(tmp.event(&e0));
+  HIPCHK(tmp.event(&e1));
   for (int k = 0; k < 2; ++k) CHK(ctx->k_launch(which, x, g, col, head));
   HIPCHK(hipEventRecord(e0, ctx->q.stream));
   for (int k = 0; k < reps; ++k) CHK(ctx->k_launch(which, x, g, col, head));
@@ -414,8 +414,6 @@ int lbfgsb_hip_kernel_time(lbfgsb_hip_ctx *ctx, int which, const void *x, const 
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *h_ms_per_launch = (double)ms / reps;
   return 0;
 }
@@ -591,7 +589,7 @@ struct HostRegistry {
   int32_t next_id = 1;
   // Contexts of runs that were abandoned without lbfgsb_hip_release_host (the reference's driver2 /
   // driver3 leave with task = 'STOP' and never re-enter setulb) are NOT destroyed from this static
-  // object's destructor: hipFree / hipStreamDestroy / ncclCommDestroy at process exit are unordered
+  // object's destructor: GpuOwner's frees / hipStreamDestroy / ncclCommDestroy at process exit are unordered
   // against the HIP runtime's own teardown and can fault or hang.  The process exit reclaims them.
   ~HostRegistry() { live.clear(); }
   int32_t add(lbfgsb_hip_ctx *c) {
@@ -703,6 +701,18 @@ static int setulb_host_impl(int64_t n, int64_t m, void *x, const void *l, const 
       for (int k = 0; k < 16; ++k) puti(isave_, k, off64[k]);
     for (int k = 0; k < 4; ++k) puti(lsave_, k, lsave[k]);
   };
+  // the caller's nbd as the int32 array the device reads, narrowed from int64 where need be (values outside
+  // int32 are invalid bound types anyway: errclb reports them)
+  auto upload_nbd = [&](int32_t *dst) -> int {
+    std::vector<int32_t> nb;
+    if (i8) {
+      nb.resize((size_t)n);
+      const int64_t *src = (const int64_t *)nbd_;
+      for (int64_t k = 0; k < n; ++k) nb[(size_t)k] = (src[k] < 0 || src[k] > 3) ? -1 : (int32_t)src[k];
+    }
+    HIPCHK(hipMemcpy(dst, i8 ? (const void *)nb.data() : nbd_, (size_t)n * 4, hipMemcpyHostToDevice));
+    return 0;
+  };
   lbfgsb_hip_ctx *ctx = nullptr;
   const bool start = lbh::str60_eq(task, "START");
   if (start) {
@@ -749,25 +759,16 @@ static int setulb_host_impl(int64_t n, int64_t m, void *x, const void *l, const 
     if (iteration_file && iteration_file[0]) ctx->itfile_name = iteration_file;
     const size_t vb = ((size_t)n + 32) * rb;
     auto stage = [&]() -> int {
-      HIPCHK(hipMalloc(&ctx->hx, vb));
-      HIPCHK(hipMalloc(&ctx->hg, vb));
-      HIPCHK(hipMalloc(&ctx->hl, vb));
-      HIPCHK(hipMalloc(&ctx->hu, vb));
-      HIPCHK(hipMalloc(&ctx->hnbd, ((size_t)n + 32) * 4));
+      HIPCHK(ctx->own.device(&ctx->hx, vb));
+      HIPCHK(ctx->own.device(&ctx->hg, vb));
+      HIPCHK(ctx->own.device(&ctx->hl, vb));
+      HIPCHK(ctx->own.device(&ctx->hu, vb));
+      HIPCHK(ctx->own.device(&ctx->hnbd, ((size_t)n + 32) * 4));
       HIPCHK(hipMemset(ctx->hg, 0, vb));
       HIPCHK(hipMemcpy(ctx->hx, x, (size_t)n * rb, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(ctx->hl, l, (size_t)n * rb, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(ctx->hu, u, (size_t)n * rb, hipMemcpyHostToDevice));
-      if (i8) {  // (values outside int32 are invalid bound types anyway: errclb reports them)
-        std::vector<int32_t> nb((size_t)n);
-        const int64_t *src = (const int64_t *)nbd_;
-        for (int64_t k = 0; k < n; ++k)
-          nb[(size_t)k] = (src[k] < 0 || src[k] > 3) ? -1 : (int32_t)src[k];
-        HIPCHK(hipMemcpy(ctx->hnbd, nb.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-      } else {
-        HIPCHK(hipMemcpy(ctx->hnbd, nbd_, (size_t)n * 4, hipMemcpyHostToDevice));
-      }
-      return 0;
+      return upload_nbd(ctx->hnbd);
     };
     rc = stage();
     if (rc) {
@@ -793,28 +794,19 @@ static int setulb_host_impl(int64_t n, int64_t m, void *x, const void *l, const 
     if (lbh::str60_pre(task, "NEW_X") && (isave[29] == 1 || (isave[29] > 0 && isave[29] % 32 == 0))) {
       void *tl = nullptr, *tu = nullptr;
       int32_t *tn = nullptr;
+      GpuOwner tmp;  // (the three copies go when this check is left, whichever way)
       double ndiff = 0.0;
       auto check = [&]() -> int {
         const size_t vb = ((size_t)n + 32) * rb;
-        HIPCHK(hipMalloc(&tl, vb));
-        HIPCHK(hipMalloc(&tu, vb));
-        HIPCHK(hipMalloc(&tn, ((size_t)n + 32) * 4));
+        HIPCHK(tmp.device(&tl, vb));
+        HIPCHK(tmp.device(&tu, vb));
+        HIPCHK(tmp.device(&tn, ((size_t)n + 32) * 4));
         HIPCHK(hipMemcpy(tl, l, (size_t)n * rb, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(tu, u, (size_t)n * rb, hipMemcpyHostToDevice));
-        if (i8) {
-          std::vector<int32_t> nb((size_t)n);
-          const int64_t *src = (const int64_t *)nbd_;
-          for (int64_t k = 0; k < n; ++k) nb[(size_t)k] = (src[k] < 0 || src[k] > 3) ? -1 : (int32_t)src[k];
-          HIPCHK(hipMemcpy(tn, nb.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-        } else {
-          HIPCHK(hipMemcpy(tn, nbd_, (size_t)n * 4, hipMemcpyHostToDevice));
-        }
+        CHK(upload_nbd(tn));
         return ctx->bounds_same(ctx->hl, ctx->hu, ctx->hnbd, tl, tu, tn, &ndiff);
       };
       int rcc = check();
-      if (tl) (void)hipFree(tl);
-      if (tu) (void)hipFree(tu);
-      if (tn) (void)hipFree(tn);
       if (rcc && (!tl || !tu || !tn)) {
         // no room for the three temporary copies (a run that fits must not fail for a CHECK): skipped this time
         (void)hipGetLastError();

@@ -156,41 +156,14 @@ class Solver final : public lbfgsb_hip_ctx {
   ~Solver() override { release(); }
 
   void release() {
-    qn_release();
-    kkt_release();
     if (debug_walk && n_mid > 0)
       std::fprintf(stderr, "[host] %lld stretches, us each: linesearch+return %.1f | caller %.1f | update %.1f | "
                            "cauchy+freev %.1f | formk+subsm algebra %.1f | all %.1f\n",
                    (long long)n_mid, t_seg[0] / n_mid * 1e6, t_seg[1] / n_mid * 1e6, t_seg[2] / n_mid * 1e6,
                    t_seg[3] / n_mid * 1e6, t_seg[4] / n_mid * 1e6, t_mid / n_mid * 1e6);
-    auto F = [](auto *&p) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-    };
-    F(ws), F(wy), F(lmask), F(zero_buf), F(z), F(r_own), F(d), F(t_own), F(xp), F(tbrk), F(iwhere), F(nbd8), F(index), F(indx2),
-        F(scan_tmp), F(wasfree), F(prevfree), F(keys[0]), F(keys[1]), F(idx[0]), F(idx[1]),
-        F(sort_tmp), F(d_count), F(d_chg), F(d_msg), F(d_msg2), F(d_msg_all), F(q.d_part), F(q.d_res), F(q.d_gpart),
-        F(q.d_part_alt[0]), F(q.d_part_alt[1]), F(q.d_fin_count), F(d_fcount), F(wide_rows),
-        F(d_fix), F(pg_buf), F(pg_tmp), F(sp_keys), F(sp_idx), F(sp_count), F(sp_msg), F(sp_msg_all), F(d_res_all),
-        F(ub_buf), F(mg_keys[0]), F(mg_keys[1]), F(mg_vals[0]), F(mg_vals[1]), F(mg_tmp), F(d_merged);
-    F(hx), F(hg), F(hl), F(hu), F(hnbd), F(l_snap), F(u_snap);
-    auto H = [](auto *&p) {
-      if (p) (void)hipHostFree(p);
-      p = nullptr;
-    };
-    H(h_count), H(h_msg_all), H(h_msg_loc), H(h_hdr), H(h_res), H(h_flag), H(h_pub), H(h_fin_flag), H(h_fix), H(h_sp_all), H(h_sp_loc), H(h_res_all);
-    if (pf_ev) (void)hipEventDestroy(pf_ev);
-    pf_ev = nullptr;
-    if (order_ev) (void)hipEventDestroy(order_ev);
-    order_ev = nullptr;
-    if (return_ev) (void)hipEventDestroy(return_ev);
-    return_ev = nullptr;
-    for (auto &ring : clk_ev)
-      for (auto &pair : ring)
-        for (auto &e : pair) {
-          if (e) (void)hipEventDestroy(e);
-          e = nullptr;
-        }
+    // every buffer and event of the context (the operators' and the host entry's included), in front of the
+    // communicator and the stream they were used on
+    own.release_all();
     if (comm && g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
     comm = nullptr;
     if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -221,46 +194,34 @@ class Solver final : public lbfgsb_hip_ctx {
     // streamed-once data: nontemporal loads unless W fits the 256 MiB Infinity Cache
     q.nt = (size_t)2 * ld * m * sizeof(T) > ((size_t)192 << 20);
     const size_t wbytes = (size_t)ld * m * sizeof(T);
-    HIPCHK(hipMalloc(&ws, wbytes));
-    HIPCHK(hipMalloc(&wy, wbytes));
-    HIPCHK(hipMemsetAsync(ws, 0, wbytes, stream));
-    HIPCHK(hipMemsetAsync(wy, 0, wbytes, stream));
+    HIPCHK(own.device_zeroed(&ws, wbytes, stream));
+    HIPCHK(own.device_zeroed(&wy, wbytes, stream));
     {
       const size_t nw = (size_t)((n + lbk::CW_TILE - 1) / lbk::CW_TILE) * (lbk::CW_TILE / 64) + 4;
-      HIPCHK(hipMalloc(&lmask, nw * sizeof(uint64_t)));
-      HIPCHK(hipMemsetAsync(lmask, 0, nw * sizeof(uint64_t), stream));
+      HIPCHK(own.device_zeroed(&lmask, nw * sizeof(uint64_t), stream));
       lbk::launch_lmask_ones(q, n, lmask);
     }
-    HIPCHK(hipMalloc(&ub_buf, 192));
+    HIPCHK(own.device(&ub_buf, 192));
     // read by the unroll slots beyond the stored pairs (16 bytes per lane from its start; under the tile-local
     // layout of W at a lane's in-tile slot: a tile of the widest kind long)
-    HIPCHK(hipMalloc(&zero_buf, 2048));
-    HIPCHK(hipMemsetAsync(zero_buf, 0, 2048, stream));
+    HIPCHK(own.device_zeroed(&zero_buf, 2048, stream));
     const size_t vb = (size_t)(n + 32) * sizeof(T);
-    for (T **p : {&z, &r_own, &d, &t_own, &xp, &tbrk}) {
-      HIPCHK(hipMalloc(p, vb));
-      HIPCHK(hipMemsetAsync(*p, 0, vb, stream));
-    }
+    for (T **p : {&z, &r_own, &d, &t_own, &xp, &tbrk}) HIPCHK(own.device_zeroed(p, vb, stream));
     t = t_own, r = r_own;
     if (follow_on)
-      for (T **p : {&l_snap, &u_snap}) {
-        HIPCHK(hipMalloc(p, vb));
-        HIPCHK(hipMemsetAsync(*p, 0, vb, stream));
-      }
-    HIPCHK(hipMalloc(&iwhere, (size_t)(n + 32) * sizeof(lbk::iw_t)));
-    HIPCHK(hipMalloc(&nbd8, (size_t)(n + 32) * sizeof(lbk::nb_t)));
+      for (T **p : {&l_snap, &u_snap}) HIPCHK(own.device_zeroed(p, vb, stream));
+    HIPCHK(own.device(&iwhere, (size_t)(n + 32) * sizeof(lbk::iw_t)));
+    HIPCHK(own.device(&nbd8, (size_t)(n + 32) * sizeof(lbk::nb_t)));
     HIPCHK(hipMemsetAsync(iwhere, 0, (size_t)(n + 32) * sizeof(lbk::iw_t), stream));
-    HIPCHK(hipMalloc(&wasfree, (size_t)n + 32));
+    HIPCHK(own.device(&wasfree, (size_t)n + 32));
     HIPCHK(hipMemsetAsync(wasfree, 1, (size_t)n + 32, stream));
     if (flags & LBFGSB_F_MIRROR_INDEX) {
-      HIPCHK(hipMalloc(&prevfree, (size_t)n + 32));
+      HIPCHK(own.device(&prevfree, (size_t)n + 32));
       HIPCHK(hipMemsetAsync(prevfree, 1, (size_t)n + 32, stream));
-      HIPCHK(hipMalloc(&index, (size_t)n * sizeof(int32_t)));
-      HIPCHK(hipMalloc(&indx2, (size_t)n * sizeof(int32_t)));
-      HIPCHK(hipMemsetAsync(index, 0, (size_t)n * sizeof(int32_t), stream));
-      HIPCHK(hipMemsetAsync(indx2, 0, (size_t)n * sizeof(int32_t), stream));
+      HIPCHK(own.device_zeroed(&index, (size_t)n * sizeof(int32_t), stream));
+      HIPCHK(own.device_zeroed(&indx2, (size_t)n * sizeof(int32_t), stream));
       const size_t nch = (size_t)((n + 1023) / 1024) + 2;
-      HIPCHK(hipMalloc(&scan_tmp, 3 * nch * sizeof(int32_t)));
+      HIPCHK(own.device(&scan_tmp, 3 * nch * sizeof(int32_t)));
     }
     // reduction scratch
     const size_t E = (size_t)2 * m * m + m;
@@ -273,45 +234,43 @@ class Solver final : public lbfgsb_hip_ctx {
     //  speculative freev counts + formk patch of a trial point: 4 + E + 1)
     res_len = std::max<size_t>(std::max<size_t>(lbk::RES_MAX, E) + 8, (size_t)SPEC_OFF + 4 + E + 1 + 8);
     res_len = std::max<size_t>(res_len, lbk::split_res_len(m));  // (the parts of a split update pass)
-    HIPCHK(hipMalloc(&q.d_part, (size_t)lbk::RES_MAX * lbk::MAX_BLOCKS * sizeof(double)));
-    HIPCHK(hipMalloc(&q.d_res, res_len * sizeof(double)));
-    HIPCHK(hipMalloc(&q.d_gpart, (E + 1) * lbk::GRAM_BLOCKS * sizeof(double)));  // (+ the eager patch's flag slot)
-    HIPCHK(hipHostMalloc(&h_res, res_len * sizeof(double)));
+    HIPCHK(own.device(&q.d_part, (size_t)lbk::RES_MAX * lbk::MAX_BLOCKS * sizeof(double)));
+    HIPCHK(own.device(&q.d_res, res_len * sizeof(double)));
+    HIPCHK(own.device(&q.d_gpart, (E + 1) * lbk::GRAM_BLOCKS * sizeof(double)));  // (+ the eager patch's flag slot)
+    HIPCHK(own.pinned(&h_res, res_len * sizeof(double)));
     HIPCHK(hipHostGetDevicePointer((void **)&hd_res, h_res, 0));
-    HIPCHK(hipHostMalloc(&h_flag, 64));
+    HIPCHK(own.pinned(&h_flag, 64));
     std::memset(h_flag, 0, 64);
     HIPCHK(hipHostGetDevicePointer((void **)&hd_flag, h_flag, 0));
     // finalize as publisher: the host mirror of d_res, its sequence word, the workgroup counter; two small
     // partial-sum matrices for kernels whose finalize is parked (kernels.hpp, Queue)
-    HIPCHK(hipHostMalloc(&h_pub, res_len * sizeof(double)));
+    HIPCHK(own.pinned(&h_pub, res_len * sizeof(double)));
     HIPCHK(hipHostGetDevicePointer((void **)&q.hd_pub, h_pub, 0));
-    HIPCHK(hipHostMalloc(&h_fin_flag, 64));
+    HIPCHK(own.pinned(&h_fin_flag, 64));
     std::memset(h_fin_flag, 0, 64);
     HIPCHK(hipHostGetDevicePointer((void **)&q.hd_fin_flag, h_fin_flag, 0));
-    HIPCHK(hipMalloc(&q.d_fin_count, 64));
-    HIPCHK(hipMemsetAsync(q.d_fin_count, 0, 64, stream));
+    HIPCHK(own.device_zeroed(&q.d_fin_count, 64, stream));
     for (double *&pa : q.d_part_alt)
-      HIPCHK(hipMalloc(&pa, (size_t)lbk::Queue::ALT_SLOTS * lbk::MAX_BLOCKS * sizeof(double)));
+      HIPCHK(own.device(&pa, (size_t)lbk::Queue::ALT_SLOTS * lbk::MAX_BLOCKS * sizeof(double)));
     q.fin_publish = spin_on;
     // cauchy selection scratch (window mode); the full-sort buffers grow on demand
     CHK(ensure_sel(SEL_CAP));
-    HIPCHK(hipMalloc(&d_count, sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_fcount, 64));
-    HIPCHK(hipMemsetAsync(d_fcount, 0, 64, stream));
+    HIPCHK(own.device(&d_count, sizeof(uint32_t)));
+    HIPCHK(own.device_zeroed(&d_fcount, 64, stream));
     h_loc.assign(res_len, 0.0);
-    HIPCHK(hipMalloc(&d_chg, (size_t)CHG_CAP * sizeof(uint32_t)));
-    HIPCHK(hipHostMalloc(&h_count, sizeof(uint32_t)));
+    HIPCHK(own.device(&d_chg, (size_t)CHG_CAP * sizeof(uint32_t)));
+    HIPCHK(own.pinned(&h_count, sizeof(uint32_t)));
     msg_len = 2 + (size_t)CHUNK_MAX * (2 * m + 4);
-    HIPCHK(hipMalloc(&d_msg, msg_len * sizeof(double)));
-    HIPCHK(hipMalloc(&d_msg2, msg_len * sizeof(double)));
-    HIPCHK(hipEventCreateWithFlags(&pf_ev, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc(&h_hdr, 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&sp_keys, SPEC_CAP * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&sp_idx, SPEC_CAP * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&sp_count, sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&sp_msg, (2 + (size_t)SPEC_CAP * (2 * m_ + 4)) * sizeof(double)));
-    HIPCHK(hipMalloc(&d_fix, FIX_CAP * sizeof(int64_t)));
-    HIPCHK(hipHostMalloc(&h_fix, FIX_CAP * sizeof(int64_t)));
+    HIPCHK(own.device(&d_msg, msg_len * sizeof(double)));
+    HIPCHK(own.device(&d_msg2, msg_len * sizeof(double)));
+    HIPCHK(own.event(&pf_ev, hipEventDisableTiming));
+    HIPCHK(own.pinned(&h_hdr, 2 * sizeof(double)));
+    HIPCHK(own.device(&sp_keys, SPEC_CAP * sizeof(uint64_t)));
+    HIPCHK(own.device(&sp_idx, SPEC_CAP * sizeof(uint32_t)));
+    HIPCHK(own.device(&sp_count, sizeof(uint32_t)));
+    HIPCHK(own.device(&sp_msg, (2 + (size_t)SPEC_CAP * (2 * m_ + 4)) * sizeof(double)));
+    HIPCHK(own.device(&d_fix, FIX_CAP * sizeof(int64_t)));
+    HIPCHK(own.pinned(&h_fix, FIX_CAP * sizeof(int64_t)));
     CHK(set_ranks(0, 1));
     sy.assign((size_t)m * m, 0.0);
     ss.assign((size_t)m * m, 0.0);
@@ -327,50 +286,33 @@ class Solver final : public lbfgsb_hip_ctx {
   // (re)size the all-gather landing buffers for `nr` ranks
   int set_ranks(int rk, int nr) {
     rank = rk, nranks = nr;
-    if (d_msg_all) (void)hipFree(d_msg_all);
-    if (h_msg_all) (void)hipHostFree(h_msg_all);
-    if (h_msg_loc) (void)hipHostFree(h_msg_loc);
-    d_msg_all = h_msg_all = h_msg_loc = nullptr;
-    HIPCHK(hipMalloc(&d_msg_all, (size_t)nr * msg_len * sizeof(double)));
-    HIPCHK(hipHostMalloc(&h_msg_all, (size_t)nr * mg_stride() * sizeof(double)));
-    for (auto **p : {(void **)&mg_keys[0], (void **)&mg_keys[1], (void **)&mg_vals[0], (void **)&mg_vals[1],
-                     (void **)&mg_tmp, (void **)&d_merged}) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
+    HIPCHK(own.device(&d_msg_all, (size_t)nr * msg_len * sizeof(double)));
+    HIPCHK(own.pinned(&h_msg_all, (size_t)nr * mg_stride() * sizeof(double)));
+    // (the merge buffers are sized by the ranks too: exchange_merged brings them back when it needs them)
+    own.drop(&mg_keys[0], &mg_keys[1], &mg_vals[0], &mg_vals[1], &mg_tmp, &d_merged);
     mg_slots = 0;
-    HIPCHK(hipHostMalloc(&h_msg_loc, msg_len * sizeof(double)));
-    if (sp_msg_all) (void)hipFree(sp_msg_all);
-    if (h_sp_all) (void)hipHostFree(h_sp_all);
-    if (h_sp_loc) (void)hipHostFree(h_sp_loc);
-    sp_msg_all = h_sp_all = h_sp_loc = nullptr;
-    HIPCHK(hipMalloc(&sp_msg_all, (size_t)nr * sp_len() * sizeof(double)));
-    HIPCHK(hipHostMalloc(&h_sp_all, ((size_t)nr * sp_len() + nr) * sizeof(double)));
-    HIPCHK(hipHostMalloc(&h_sp_loc, sp_len() * sizeof(double)));
+    HIPCHK(own.pinned(&h_msg_loc, msg_len * sizeof(double)));
+    HIPCHK(own.device(&sp_msg_all, (size_t)nr * sp_len() * sizeof(double)));
+    HIPCHK(own.pinned(&h_sp_all, ((size_t)nr * sp_len() + nr) * sizeof(double)));
+    HIPCHK(own.pinned(&h_sp_loc, sp_len() * sizeof(double)));
     spcand.valid = false;
-    if (d_res_all) (void)hipFree(d_res_all);
-    if (h_res_all) (void)hipHostFree(h_res_all);
-    d_res_all = h_res_all = nullptr;
-    HIPCHK(hipMalloc(&d_res_all, (size_t)nr * res_len * sizeof(double)));
-    HIPCHK(hipHostMalloc(&h_res_all, (size_t)nr * res_len * sizeof(double)));
+    HIPCHK(own.device(&d_res_all, (size_t)nr * res_len * sizeof(double)));
+    HIPCHK(own.pinned(&h_res_all, (size_t)nr * res_len * sizeof(double)));
     HIPCHK(hipHostGetDevicePointer((void **)&hd_res_all, h_res_all, 0));
     return 0;
   }
 
   int ensure_sel(size_t count) {
     if (count <= sel_alloc) return 0;
-    auto F = [](auto *&p) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-    };
-    F(keys[0]), F(keys[1]), F(idx[0]), F(idx[1]), F(sort_tmp);
+    // (all five go before the first comes back: a grow to n elements never holds both generations)
+    own.drop(&keys[0], &keys[1], &idx[0], &idx[1], &sort_tmp);
     sel_alloc = 0;
     for (int k = 0; k < 2; ++k) {
-      HIPCHK(hipMalloc(&keys[k], count * sizeof(uint64_t)));
-      HIPCHK(hipMalloc(&idx[k], count * sizeof(uint32_t)));
+      HIPCHK(own.device(&keys[k], count * sizeof(uint64_t)));
+      HIPCHK(own.device(&idx[k], count * sizeof(uint32_t)));
     }
     sort_tmp_bytes = lbk::sort_pairs_temp_bytes(count) + 256;
-    HIPCHK(hipMalloc(&sort_tmp, sort_tmp_bytes));
+    HIPCHK(own.device(&sort_tmp, sort_tmp_bytes));
     sel_alloc = count;
     return 0;
   }

@@ -25,6 +25,7 @@
 
 #include "../../include/lbfgsb_hip.h"
 #include "../../include/lbfgsb_hip_debug.h"
+#include "gpu_owner.hpp"
 #include "host_dense.hpp"
 #include "kernels.hpp"
 #include "report.hpp"
@@ -180,6 +181,9 @@ struct lbfgsb_hip_ctx {
   virtual int set_option(const char *name, double value) = 0;  // lbfgsb_hip_set_option
   virtual const void *prev_iterate() const = 0;  // t: the reference's wa(3n+2mn+11m^2+1 : +n)
 
+  // every device buffer, pinned buffer and event of the context, the members of Solver<T> included, is obtained
+  // through this owner and given back by its release_all() (gpu_owner.hpp; Solver::release() says when)
+  GpuOwner own;
   // host-entry staging (setulb_host)
   void *hx = nullptr, *hg = nullptr, *hl = nullptr, *hu = nullptr;
   int32_t *hnbd = nullptr;
@@ -278,8 +282,8 @@ struct lbfgsb_hip_ctx {
     if (clk_pending[k][s]) clk_dropped++, clk_pending[k][s] = false;
     clk_cur[k] = s;
     if (!clk_ev[k][s][0]) {
-      (void)hipEventCreate(&clk_ev[k][s][0]);
-      (void)hipEventCreate(&clk_ev[k][s][1]);
+      (void)own.event(&clk_ev[k][s][0]);
+      (void)own.event(&clk_ev[k][s][1]);
     }
     (void)hipEventRecord(clk_ev[k][s][0], clk_stream);
   }

@@ -27,17 +27,6 @@
                     LBFGSB_KKT_GFREE_MAX == lbk::KktSlots::gfree_max() - lbk::KktSlots::nsum(),
                 "LBFGSB_KKT_* and KktSlots disagree");
 
-  void kkt_release() {
-    auto F = [](auto *&p) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-    };
-    F(kk.d_part), F(kk.d_res), F(kk.d_res_all), F(kk.d_tmp);
-    kk.all_ranks = 0;
-    if (kk.h_res) (void)hipHostFree(kk.h_res);
-    if (kk.h_count) (void)hipHostFree(kk.h_count);
-    kk.h_res = nullptr, kk.h_count = nullptr;
-  }
   // the refusals of both entries (nothing has been touched when they return), then the buffers
   int kkt_ready(const char *who) {
     if (defer_live)
@@ -47,20 +36,19 @@
       return fail(LBFGSB_E_STATE, std::string(who) + ": a built-in objective's value is still on the device: call "
                                                      "after the next setulb call has collected it");
     HIPCHK(hipSetDevice(device));
-    if (!kk.d_part) {
-      HIPCHK(hipMalloc(&kk.d_part, (size_t)KKT_RES * lbk::MAX_BLOCKS * sizeof(double)));
-      HIPCHK(hipMalloc(&kk.d_res, (size_t)KKT_RES * sizeof(double)));
-      HIPCHK(hipMalloc(&kk.d_tmp, (size_t)(lbk::kkt_list_chunks(n) + 1) * sizeof(int64_t)));
-      HIPCHK(hipHostMalloc(&kk.h_count, sizeof(int64_t), hipHostMallocDefault));
+    if (!kk.h_count) {  // (the last of the four: a call that failed part-way starts over)
+      HIPCHK(own.device(&kk.d_part, (size_t)KKT_RES * lbk::MAX_BLOCKS * sizeof(double)));
+      HIPCHK(own.device(&kk.d_res, (size_t)KKT_RES * sizeof(double)));
+      HIPCHK(own.device(&kk.d_tmp, (size_t)(lbk::kkt_list_chunks(n) + 1) * sizeof(int64_t)));
+      HIPCHK(own.pinned(&kk.h_count, sizeof(int64_t)));
     }
     // the gather space follows the communicator of THIS call (one may be attached after an earlier call)
     const int want = comm ? nranks : 1;
     if (kk.all_ranks != want) {
-      if (kk.d_res_all) HIPCHK(hipFree(kk.d_res_all));
-      if (kk.h_res) HIPCHK(hipHostFree(kk.h_res));
-      kk.d_res_all = nullptr, kk.h_res = nullptr, kk.all_ranks = 0;
-      if (comm) HIPCHK(hipMalloc(&kk.d_res_all, (size_t)KKT_RES * nranks * sizeof(double)));
-      HIPCHK(hipHostMalloc(&kk.h_res, (size_t)KKT_RES * (want + 1) * sizeof(double), hipHostMallocDefault));
+      kk.all_ranks = 0;
+      own.drop(&kk.d_res_all);
+      if (comm) HIPCHK(own.device(&kk.d_res_all, (size_t)KKT_RES * nranks * sizeof(double)));
+      HIPCHK(own.pinned(&kk.h_res, (size_t)KKT_RES * (want + 1) * sizeof(double)));
       kk.all_ranks = want;
     }
     return 0;

@@ -53,11 +53,10 @@
     const size_t bytes = (narr * (size_t)nbp + gath + small) * sizeof(double);
     bool fits = true;
     if (bytes > pg_bytes) {
-      if (pg_buf) (void)hipFree(pg_buf);
-      pg_buf = nullptr, pg_bytes = 0;
+      own.drop(&pg_buf), pg_bytes = 0;  // (in front of the question how much is free)
       size_t mfree = 0, mtotal = 0;
       (void)hipMemGetInfo(&mfree, &mtotal);
-      if (bytes > mfree / 10 * 9 || hipMalloc(&pg_buf, bytes) != hipSuccess) {
+      if (bytes > mfree / 10 * 9 || own.device(&pg_buf, bytes) != hipSuccess) {
         (void)hipGetLastError();
         fits = false;
       } else {
@@ -69,11 +68,9 @@
     //  collective)
     const size_t tb = std::max(lbk::scan_temp_bytes((size_t)nb), lbk::f2scan_temp_bytes((size_t)nb)) + 256;
     if (fits && tb > pg_tmp_bytes) {
-      if (pg_tmp) (void)hipFree(pg_tmp);
-      pg_tmp = nullptr, pg_tmp_bytes = 0;
-      if (hipMalloc(&pg_tmp, tb) != hipSuccess) {
+      pg_tmp_bytes = 0;
+      if (own.device(&pg_tmp, tb) != hipSuccess) {
         (void)hipGetLastError();
-        pg_tmp = nullptr;
         fits = false;
       } else {
         pg_tmp_bytes = tb;

@@ -409,11 +409,10 @@
       std::vector<double> mine((size_t)nmax, -1.0);
       for (int64_t i = 0; i < n; ++i) mine[(size_t)i] = (double)tb[(size_t)i];
       double *dsend = nullptr, *drecv = nullptr;
-      HIPCHK(hipMalloc(&dsend, (size_t)nmax * sizeof(double)));
-      if (hipMalloc(&drecv, (size_t)nmax * nranks * sizeof(double)) != hipSuccess) {
-        (void)hipFree(dsend);
+      GpuOwner tmp;  // (gives both back on every way out)
+      HIPCHK(tmp.device(&dsend, (size_t)nmax * sizeof(double)));
+      if (tmp.device(&drecv, (size_t)nmax * nranks * sizeof(double)) != hipSuccess)
         return fail(LBFGSB_E_NOGPU, "exact tie order: no memory for the gathered breakpoint times");
-      }
       tall.resize((size_t)nmax * nranks);
       int rc = 0;
       if (hipMemcpy(dsend, mine.data(), (size_t)nmax * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
@@ -422,7 +421,6 @@
       if (!rc && hipStreamSynchronize(stream) != hipSuccess) rc = fail(LBFGSB_E_NOGPU, "exact tie order: sync");
       if (!rc && hipMemcpy(tall.data(), drecv, tall.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(LBFGSB_E_NOGPU, "exact tie order: download failed");
-      (void)hipFree(dsend), (void)hipFree(drecv);
       if (rc) return rc;
     } else {
       pv.hrow0[0] = row0;
@@ -537,20 +535,15 @@
     const size_t S = (size_t)nranks * chunk;
     if (S > mg_slots) {
       const size_t cap = (size_t)nranks * ((msg_len - 2) / 4);  // the longest chunks there are (recl = 4)
-      auto F = [](auto *&p) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-      };
-      F(mg_keys[0]), F(mg_keys[1]), F(mg_vals[0]), F(mg_vals[1]), F(mg_tmp), F(d_merged);
       mg_slots = 0;
       mg_tmp_bytes = lbk::sort_pairs_temp_bytes(cap) + 256;
-      bool ok = hipMalloc(&mg_keys[0], cap * 8) == hipSuccess && hipMalloc(&mg_keys[1], cap * 8) == hipSuccess &&
-                hipMalloc(&mg_vals[0], cap * 4) == hipSuccess && hipMalloc(&mg_vals[1], cap * 4) == hipSuccess &&
-                hipMalloc(&mg_tmp, mg_tmp_bytes) == hipSuccess &&
-                hipMalloc(&d_merged, (size_t)nranks * mg_stride() * sizeof(double)) == hipSuccess;
+      bool ok = own.device(&mg_keys[0], cap * 8) == hipSuccess && own.device(&mg_keys[1], cap * 8) == hipSuccess &&
+                own.device(&mg_vals[0], cap * 4) == hipSuccess && own.device(&mg_vals[1], cap * 4) == hipSuccess &&
+                own.device(&mg_tmp, mg_tmp_bytes) == hipSuccess &&
+                own.device(&d_merged, (size_t)nranks * mg_stride() * sizeof(double)) == hipSuccess;
       if (!ok) {
         (void)hipGetLastError();
-        F(mg_keys[0]), F(mg_keys[1]), F(mg_vals[0]), F(mg_vals[1]), F(mg_tmp), F(d_merged);
+        own.drop(&mg_keys[0], &mg_keys[1], &mg_vals[0], &mg_vals[1], &mg_tmp, &d_merged);
         // (every rank must take the same route: without the buffers HERE the run cannot go on in step)
         return fail(LBFGSB_E_ALLOC, "no memory for the merge buffers of the breakpoint exchange");
       }

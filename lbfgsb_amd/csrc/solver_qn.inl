@@ -40,30 +40,19 @@
     qn.have = true, qn.col = col, qn.head = head, qn.theta = theta, qn.theta_gram = false;
     qn.iupdat = iupdat, qn.nref = nrefresh;
   }
-  void qn_release() {
-    auto F = [](double *&p) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-    };
-    F(qn.d_part), F(qn.d_res), F(qn.d_res_all), F(qn.d_n[0]), F(qn.d_n[1]);
-    qn.all_ranks = 0;
-    if (qn.h_n) (void)hipHostFree(qn.h_n);
-    qn.h_n = nullptr;
-  }
   int qn_alloc() {
-    if (!qn.d_part) {
-      HIPCHK(hipMalloc(&qn.d_part, (size_t)2 * lbk::QN_TILE * lbk::QN_KMAX * lbk::MAX_BLOCKS * sizeof(double)));
-      HIPCHK(hipMalloc(&qn.d_res, (size_t)QN_RES * sizeof(double)));
-      HIPCHK(hipMalloc(&qn.d_n[0], (size_t)QN_NP * sizeof(double)));
-      HIPCHK(hipMalloc(&qn.d_n[1], (size_t)QN_NP * sizeof(double)));
-      HIPCHK(hipHostMalloc(&qn.h_n, (size_t)QN_NP * sizeof(double), hipHostMallocDefault));
+    if (!qn.h_n) {  // (the last of the five: a call that failed part-way starts over)
+      HIPCHK(own.device(&qn.d_part, (size_t)2 * lbk::QN_TILE * lbk::QN_KMAX * lbk::MAX_BLOCKS * sizeof(double)));
+      HIPCHK(own.device(&qn.d_res, (size_t)QN_RES * sizeof(double)));
+      HIPCHK(own.device(&qn.d_n[0], (size_t)QN_NP * sizeof(double)));
+      HIPCHK(own.device(&qn.d_n[1], (size_t)QN_NP * sizeof(double)));
+      HIPCHK(own.pinned(&qn.h_n, (size_t)QN_NP * sizeof(double)));
       qn.h_res.assign(QN_RES, 0.0);
     }
     // the gather space follows the communicator of THIS call (one may be attached after an earlier call)
     if (comm && qn.all_ranks != nranks) {
-      if (qn.d_res_all) HIPCHK(hipFree(qn.d_res_all));
-      qn.d_res_all = nullptr, qn.all_ranks = 0;
-      HIPCHK(hipMalloc(&qn.d_res_all, (size_t)QN_RES * nranks * sizeof(double)));
+      qn.all_ranks = 0;
+      HIPCHK(own.device(&qn.d_res_all, (size_t)QN_RES * nranks * sizeof(double)));
       qn.all_ranks = nranks;
     }
     if (qn.h_all.size() < (size_t)QN_RES * nranks) qn.h_all.assign((size_t)QN_RES * nranks, 0.0);

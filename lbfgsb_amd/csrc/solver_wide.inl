@@ -109,9 +109,8 @@ int wide_formk_incr(int col, int head, bool updatd, int iupdat, bool &done, cons
     if (nl > 0) {
       const size_t need = (size_t)nl * 2 * upcl;
       if (need > wide_rows_cap) {
-        if (wide_rows) (void)hipFree(wide_rows);
-        wide_rows = nullptr, wide_rows_cap = 0;
-        HIPCHK(hipMalloc(&wide_rows, need * sizeof(double)));
+        wide_rows_cap = 0;
+        HIPCHK(own.device(&wide_rows, need * sizeof(double)));
         wide_rows_cap = need;
       }
       const uint32_t *lst = lbk::launch_sort_u32(q, sort_tmp, sort_tmp_bytes, d_chg, idx[1], nl);

@@ -22,6 +22,8 @@
 // fixed variables, lattice data with many equal breakpoints, first iterations with ~n segments), each NEW_X
 // state fed to lbo_cauchy and to the library's cauchy() with the same x, g, W, Sy, Wt, theta, iwhere; compared:
 // iwhere and nseg exactly, xcp / p / c / wbp / v to 1e-10 / 1e-9, info.
+// And who owns what: the stand-in runtime tracks every resource with its kind (below), every allocating call of a
+// context's creation and of the calls that regrow buffers fails once (alloc_failures), nothing is live at exit.
 #include "../../lbfgsb_amd/csrc/solver.hip"
 
 #include <atomic>
@@ -34,20 +36,70 @@ extern "C" {
 }
 
 // ============================================================ HIP runtime stand-in (host memory, synchronous)
+// Strict about ownership: every live "device" pointer, pinned pointer, event and stream stands in one table with its
+// kind.  Giving back what is not live -- never obtained, given back before, or of another kind (hipFree of pinned
+// memory, ...) -- prints and aborts; null is a no-op, as in HIP.  What is still in the table when main() ends has
+// leaked.  A countdown makes the k-th call among hipMalloc / hipHostMalloc / hipEventCreate* fail (alloc_failures).
+namespace {
+enum ResKind { RES_DEVICE, RES_PINNED, RES_EVENT, RES_STREAM };
+struct ResTable {
+  std::mutex mu;
+  std::unordered_map<void *, ResKind> live;
+  long nalloc = 0;   // calls of the three allocating kinds so far
+  long fail_at = 0;  // the call with this number (counted from the moment it is set) fails; 0: none
+  static const char *name(ResKind k) {
+    static const char *const names[] = {"device pointer", "pinned pointer", "event", "stream"};
+    return names[k];
+  }
+  // -> false: this allocating call is the one that has to fail
+  bool admit() {
+    std::lock_guard<std::mutex> lock(mu);
+    ++nalloc;
+    return !(fail_at > 0 && --fail_at == 0);
+  }
+  void *add(void *p, ResKind k) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (p) live[p] = k;
+    return p;
+  }
+  void remove(void *p, ResKind k, const char *call) {
+    if (!p) return;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = live.find(p);
+    if (it == live.end() || it->second != k) {
+      std::fprintf(stderr, "walk_check: %s(%p): not a live %s (%s%s)\n", call, p, name(k),
+                   it == live.end() ? "never obtained, or given back already" : "it is a live ",
+                   it == live.end() ? "" : name(it->second));
+      std::abort();
+    }
+    live.erase(it);
+  }
+  size_t count() {
+    std::lock_guard<std::mutex> lock(mu);
+    return live.size();
+  }
+} g_res;
+// what a failed allocating call leaves in *p: HIP promises nothing, and nobody may free it
+void *const POISON = reinterpret_cast<void *>(0x10);
+}  // namespace
 extern "C" {
 hipError_t hipMalloc(void **p, size_t bytes) {
-  *p = std::malloc(bytes ? bytes : 1);
+  if (!g_res.admit()) return *p = POISON, hipErrorOutOfMemory;
+  *p = g_res.add(std::malloc(bytes ? bytes : 1), RES_DEVICE);
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 hipError_t hipFree(void *p) {
+  g_res.remove(p, RES_DEVICE, "hipFree");
   std::free(p);
   return hipSuccess;
 }
 hipError_t hipHostMalloc(void **p, size_t bytes, unsigned int) {
-  *p = std::calloc(bytes ? bytes : 1, 1);
+  if (!g_res.admit()) return *p = POISON, hipErrorOutOfMemory;
+  *p = g_res.add(std::calloc(bytes ? bytes : 1, 1), RES_PINNED);
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 hipError_t hipHostFree(void *p) {
+  g_res.remove(p, RES_PINNED, "hipHostFree");
   std::free(p);
   return hipSuccess;
 }
@@ -79,21 +131,24 @@ hipError_t hipMemset(void *dst, int v, size_t bytes) {
   return hipSuccess;
 }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned int) {
-  *s = reinterpret_cast<hipStream_t>(new int(0));
+  *s = reinterpret_cast<hipStream_t>(g_res.add(new int(0), RES_STREAM));
   return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t s) {
+  g_res.remove(s, RES_STREAM, "hipStreamDestroy");
   delete reinterpret_cast<int *>(s);
   return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t *e) {
-  *e = reinterpret_cast<hipEvent_t>(new int(0));
+  if (!g_res.admit()) return *e = reinterpret_cast<hipEvent_t>(POISON), hipErrorOutOfMemory;
+  *e = reinterpret_cast<hipEvent_t>(g_res.add(new int(0), RES_EVENT));
   return hipSuccess;
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) {
+  g_res.remove(e, RES_EVENT, "hipEventDestroy");
   delete reinterpret_cast<int *>(e);
   return hipSuccess;
 }
@@ -1005,6 +1060,77 @@ static void run_problem(std::mt19937_64 &rng, const Problem &p, int max_iter, co
   }
 }
 
+// ============================================================ allocation failures
+// Every allocating call of a context's creation, and of the calls that (re)size buffers later, fails once: the call
+// must report it, nothing may be left in the table when the context has gone (after creation: at once, there is no
+// context), nothing may be given back twice, and the same call must succeed when it is repeated.  None of these
+// functions launches a kernel (init's launch_lmask_ones has a twin).
+struct SweepTally {
+  long counted = 0, cases = 0, failed = 0;
+  void bad(const char *what, long k, const std::string &why) {
+    failed++;
+    std::fprintf(stderr, "FAIL allocation %ld of %s: %s\n", k, what, why.c_str());
+  }
+};
+static void alloc_failures(SweepTally &st) {
+  using S = Solver<double>;
+  const int64_t n = 300;
+  auto allocs_of = [](auto &&call) {
+    const long before = g_res.nalloc;
+    call();
+    return g_res.nalloc - before;
+  };
+  for (int flags : {0, LBFGSB_F_MIRROR_INDEX | LBFGSB_F_FOLLOW_BOUNDS}) {
+    int rc = 0;
+    const long total = allocs_of([&] { delete lbfgsb_make_solver(n, n, 0, 5, flags, 0, nullptr, &rc); });
+    if (rc || g_res.count() != 0) st.bad("lbfgsb_make_solver", 0, "the undisturbed call: " + g_err);
+    st.counted += total;
+    for (long k = 1; k <= total; ++k) {
+      g_res.fail_at = k;
+      lbfgsb_hip_ctx *c = lbfgsb_make_solver(n, n, 0, 5, flags, 0, nullptr, &rc);
+      g_res.fail_at = 0;
+      st.cases++;
+      if (rc == 0 || c) st.bad("lbfgsb_make_solver", k, "no error reported");
+      delete c;
+      if (g_res.count() != 0) st.bad("lbfgsb_make_solver", k, std::to_string(g_res.count()) + " resources left");
+    }
+  }
+  static int dummy_comm;  // (a communicator: the operators' gather space over the ranks)
+  struct Op {
+    const char *name;
+    std::function<int(S *)> call;
+  };
+  auto with_comm = [](S *s) { s->comm = reinterpret_cast<ncclComm_t>(&dummy_comm), s->nranks = 2; };
+  const Op ops[] = {{"set_ranks(0, 3)", [](S *s) { return s->set_ranks(0, 3); }},
+                    {"ensure_sel(2 * SEL_CAP)", [](S *s) { return s->ensure_sel((size_t)2 * S::SEL_CAP); }},
+                    {"qn_alloc()", [&](S *s) { return with_comm(s), s->qn_alloc(); }},
+                    {"kkt_ready(\"t\")", [&](S *s) { return with_comm(s), s->kkt_ready("t"); }}};
+  for (const Op &op : ops) {
+    auto fresh = [&]() {
+      S *s = new S();
+      if (s->init(n, n, 0, 5, 0, 0, nullptr) != 0) st.bad(op.name, 0, "init: " + g_err);
+      return s;
+    };
+    S *s = fresh();
+    int rc = 0;
+    const long total = allocs_of([&] { rc = op.call(s); });
+    delete s;
+    if (rc || total < 1 || g_res.count() != 0) st.bad(op.name, 0, "the undisturbed call: " + g_err);
+    st.counted += total;
+    for (long k = 1; k <= total; ++k) {
+      s = fresh();
+      g_res.fail_at = k;
+      rc = op.call(s);
+      g_res.fail_at = 0;
+      st.cases++;
+      if (rc == 0) st.bad(op.name, k, "no error reported");
+      if (op.call(s) != 0) st.bad(op.name, k, "the repeated call failed: " + g_err);
+      delete s;
+      if (g_res.count() != 0) st.bad(op.name, k, std::to_string(g_res.count()) + " resources left");
+    }
+  }
+}
+
 int main(int argc, char **argv) {
   const int nproblems = argc > 1 ? std::atoi(argv[1]) : 60;
   const int only = argc > 2 ? std::atoi(argv[2]) : -1;  // (debugging: run this problem alone)
@@ -1074,6 +1200,12 @@ int main(int argc, char **argv) {
       }
     }
   tl.failed += starts_failed;
+  SweepTally st;
+  if (only < 0) alloc_failures(st);
+  tl.failed += st.failed;
+  std::printf("walk_check: allocation failures: %ld allocations counted, %ld cases, %ld failed\n", st.counted, st.cases,
+              st.failed);
+  std::printf("walk_check: %zu resources live at exit\n", g_res.count());
   std::printf("walk_check: %ld START cases over 1-5 ranks, %ld failed\n", starts, starts_failed);
   std::printf("walk_check: %ld cases, %ld failed, %ld stationary-point-on-a-breakpoint, %ld multi-rank, %ld in heap order, "
               "%ld walks of more than 256 segments, %ld segments in all; rank 0: %ld full sorts, %ld tie splits replayed, "

@@ -55,3 +55,14 @@ def test_walk_and_provider_under_sanitizers_against_the_oracle():
     # the one tolerated class (a stationary point that coincides with a breakpoint to the last bit: the decision
     # rests on the rounding of an n-term sum, walk_check.cpp / DESIGN.md section 7) stays rare
     assert degenerate <= max(3, cases // 50), (degenerate, cases)
+    # who owns what on the GPU: the stand-in runtime keeps a table of live device pointers, pinned pointers, events
+    # and streams and aborts on a free of the wrong kind or a second free (an abort fails the return code above);
+    # every allocating call of lbfgsb_make_solver (default flags; MIRROR_INDEX | FOLLOW_BOUNDS), set_ranks,
+    # ensure_sel, qn_alloc and kkt_ready has failed once, was reported, left nothing behind once the context was
+    # gone, and the repeated call went through; and when the program ends nothing is live
+    ma = re.search(r"walk_check: allocation failures: (\d+) allocations counted, (\d+) cases, (\d+) failed", r.stdout)
+    assert ma, r.stdout[-1500:]
+    counted, sweep_cases, sweep_failed = (int(v) for v in ma.groups())
+    assert sweep_failed == 0 and counted >= 100 and sweep_cases >= counted, r.stdout[-1500:]
+    ml = re.search(r"walk_check: (\d+) resources live at exit", r.stdout)
+    assert ml and int(ml.group(1)) == 0, r.stdout[-1500:]
