@@ -455,6 +455,32 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  *     (the Gram of A^(1/2) is qn_gram of A itself on other vectors; LBFGSB_E_ARG).
  * When, streams, the collective rule and the refusals are qn_apply's.  LBFGSB_E_ARG in addition, changing nothing:
  * NULL v / h_g, k < 1, k > LBFGSB_QN_GRAM_MAXK, ldv < n_local, ldg < k, a mode other than B / H.
+ *
+ * Eigenvalues and eigenvectors.  With the delta_i of the square root above, A has the eigenvalue alpha + delta_i
+ * with the unit eigenvector u_i = [S, Y] (N P V)_i / delta_i for every delta_i != 0, and the bulk eigenvalue alpha
+ * on the n_global - r remaining dimensions: A = alpha I + U diag(lambda - alpha) U' with orthonormal U.  A direction
+ * with |delta_i| <= LBFGSB_QN_EIG_CUT alpha counts as bulk and is not returned, so r <= min(2col, n_global); nearly
+ * parallel pairs lower r and cost no accuracy elsewhere (no division by G).  The host part is the root's (the same
+ * Gram pass, once per set of pairs; at most LBFGSB_QN_ROOT_MAXCOL stored pairs, LBFGSB_E_ARG beyond; LBFGSB_E_STATE
+ * for a model that is not positive definite, as qn_logdet).
+ *   qn_eig: *h_bulk = alpha (theta for B, 1 / theta for H), *h_r = r, and h_lambda[0 .. min(r, cap)) the r eigenvalues
+ *     alpha + delta_i in ascending order -- host doubles, the same bits on every rank.  cap = 0 with h_lambda = NULL
+ *     is the counting call.  No stored pair: r = 0.  No pass over W besides the Gram pass.  The eigenvalues of B and
+ *     of H are reciprocal up to rounding.
+ *   qn_eigvec: out + j*ldo receives the n_local rows of the unit eigenvector of eigenvalue number h_which[j], a 0-based
+ *     index into qn_eig's ascending list of the same mode, j < k <= 128; repeats are allowed, h_which = NULL means
+ *     0 .. k-1.  One pass over W per tile of 16 stored pairs writes all k vectors (fp64 sums, rounded on store in
+ *     REAL32 contexts).  The sign makes the largest coefficient of u_i in the [S, Y] basis positive (the first of
+ *     equals): a function of replicated host data, the same on every rank and for every sharding.  A repeated
+ *     eigenvalue returns some orthonormal basis of its eigenspace.
+ *     Accuracy: the bulk eigenspace has n_global - r dimensions, so a vector whose eigenvalue lies delta_i off alpha
+ *     is determined by fp64 data only up to about eps |A| / |delta_i|.  Vectors with |delta_i| >= 1e-3 alpha are
+ *     orthonormal to the accuracy of qn_apply; just above the cut (|delta_i| ~ 1e-8 alpha) the norm and the angles of
+ *     a vector may be off by 1e-6, while A u_i = lambda_i u_i still holds to the accuracy of qn_apply, because such a
+ *     vector's error lies in directions that A maps like the bulk.
+ * When, streams, the collective rule and the refusals are qn_apply's (every rank calls with its own rows).
+ * LBFGSB_E_ARG in addition, changing nothing: NULL h_r / h_bulk / out, cap < 0, cap > 0 with h_lambda = NULL, k < 1,
+ * k > 128, an index outside 0 .. r-1, ldo < n_local, a mode other than B / H.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
@@ -477,6 +503,9 @@ int lbfgsb_hip_qn_draw_logpdf(lbfgsb_hip_ctx *ctx, int mode, int64_t k, uint64_t
                               const void *mean, double scale, void *out, int64_t ldo, double *h_logp);
 int lbfgsb_hip_qn_gram(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, int64_t ldv, const void *center,
                        double *h_g, int64_t ldg);
+#define LBFGSB_QN_EIG_CUT 1e-8
+int lbfgsb_hip_qn_eig(lbfgsb_hip_ctx *ctx, int mode, int32_t cap, int32_t *h_r, double *h_bulk, double *h_lambda);
+int lbfgsb_hip_qn_eigvec(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int32_t *h_which, void *out, int64_t ldo);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.
@@ -704,6 +733,8 @@ int lbfgsb_hip_objective(lbfgsb_hip_ctx *ctx, int kind, const void *x, void *g, 
  *   "wide_incr" (0/1)       m > 32: formk adds the new pair's row and column to WN1 while no row changes status
  *                           (default 1) / from scratch whenever it runs
  *   "nt" (0/1)              nontemporal loads in the passes over W (default: by the size of W)
+ *   "qn_basis" (0/1)        qn_eigvec writes all its vectors in one pass over W per tile of 16 pairs (default 1) / goes
+ *                           through qn_apply's expansion, 4 vectors a pass: the same products summed in another order
  *   "uniform_bounds" (0/1)  detect bound arrays that hold one value each (lbfgsb_hip_uniform_bounds)
  *   "dict_bounds" (0/1)     dictionary-code bound arrays with <= 8 distinct values each (same place; default 1)
  *   "bounds_check" (0..)    compare the caller's l, u, nbd with the context's snapshot after the first iteration and

@@ -288,6 +288,18 @@ int lbfgsb_hip_qn_gram(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, 
   if (ldv < ctx->n || ldg < k) return fail(LBFGSB_E_ARG, "qn_gram: ldv < n_local or ldg < k");
   return ctx->qn_vgram(mode, k, v, ldv, center, h_g, ldg);
 }
+int lbfgsb_hip_qn_eig(lbfgsb_hip_ctx *ctx, int mode, int32_t cap, int32_t *h_r, double *h_bulk, double *h_lambda) {
+  if (!ctx || !h_r || !h_bulk) return fail(LBFGSB_E_ARG, "qn_eig: NULL argument");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_eig: mode");
+  if (cap < 0 || (cap > 0 && !h_lambda)) return fail(LBFGSB_E_ARG, "qn_eig: cap < 0, or cap > 0 without h_lambda");
+  return ctx->qn_eig(mode, cap, h_r, h_bulk, h_lambda);
+}
+int lbfgsb_hip_qn_eigvec(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int32_t *h_which, void *out, int64_t ldo) {
+  if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_eigvec: NULL argument");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_eigvec: mode");
+  if (k < 1 || k > 128 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_eigvec: k < 1, k > 128 or ldo < n_local");
+  return ctx->qn_eigvec(mode, k, h_which, out, ldo);
+}
 
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
                    const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,

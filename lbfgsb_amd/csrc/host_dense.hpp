@@ -308,12 +308,15 @@ inline int jacobi_eig(int d, double *a, double *v, double *w) {
   return -1;
 }
 
-// C (d x d, d = 2col, column-major, symmetric) and sum_i log1p(delta_i / alpha) from the Gram g = W'W and the
-// symmetric n_ of the model (both d x d).  work: 6 d^2 + d doubles.  Returns 0, -1 (the eigensolver did not
-// converge) or -2 (alpha + delta_i < -1e-8 alpha: the model is not positive definite).
-inline int qn_root(int d, double alpha, const double *g, const double *n_, double *cm, double *logsum, double *work) {
-  *logsum = 0.0;
-  if (d == 0) return 0;
+// The spectral part that the root and the eigen-decomposition share: the unit-column scaling ds = diag(G)^(1/2) (d
+// doubles), P = (D^-1 G D^-1)^(1/2), P (D N D) P = V diag(delta) V' and N P V of the scaled model.  work: 6 d^2 + d
+// doubles; on return delta is at work + 5 d^2, N P V (d x d, column i belongs to delta_i) at work, the scaled N at
+// work + 5 d^2 + d, and work + d^2 (V) is free.  clip: eigenvalues of the scaled G below d eps max(w) count as zero
+// before the square root (qn_eig's path only: the rank of [S, Y] when it has fewer rows than columns).  keep (d^2 + d
+// doubles, or NULL): the eigenvectors of the scaled G and the square roots of its eigenvalues as P was built from
+// them (copies: nothing of the arithmetic changes).  Returns 0, or -1 when the eigensolver did not converge.
+inline int qn_spectrum(int d, const double *g, const double *n_, double *ds, double *work, bool clip,
+                       double *keep = nullptr) {
   const size_t dd = (size_t)d * d;
   double *a = work, *u = work + dd, *p = work + 2 * dd, *t = work + 3 * dd, *x = work + 4 * dd, *w = work + 5 * dd;
   auto at = [d](double *m, int i, int j) -> double & { return m[i + (size_t)j * d]; };
@@ -325,8 +328,7 @@ inline int qn_root(int d, double alpha, const double *g, const double *n_, doubl
         o[i + (size_t)j * d] = s;
       }
   };
-  // unit columns: G <- D^-1 G D^-1 (in a), N <- D N D (in t, then nn), C <- D^-1 C D^-1 at the end
-  double *ds = cm;  // (cm is written last: its first d entries hold D until then)
+  // unit columns: G <- D^-1 G D^-1 (in a), N <- D N D (in t, then nn)
   for (int i = 0; i < d; ++i) ds[i] = g[i + (size_t)i * d] > 0.0 ? std::sqrt(g[i + (size_t)i * d]) : 1.0;
   for (int j = 0; j < d; ++j)
     for (int i = 0; i < d; ++i) {
@@ -335,10 +337,17 @@ inline int qn_root(int d, double alpha, const double *g, const double *n_, doubl
     }
   // P = U max(Lambda, 0)^(1/2) U'
   if (jacobi_eig(d, a, u, w) < 0) return -1;
-  for (int j = 0; j < d; ++j) {
-    const double r = std::sqrt(std::max(w[j], 0.0));
-    for (int i = 0; i < d; ++i) at(x, i, j) = at(u, i, j) * r;
+  double floor_w = 0.0;
+  if (clip) {
+    for (int j = 0; j < d; ++j) floor_w = std::max(floor_w, w[j]);
+    floor_w = floor_w * ((double)d * 2.220446049250313e-16);
   }
+  for (int j = 0; j < d; ++j) {
+    const double r = clip && w[j] < floor_w ? 0.0 : std::sqrt(std::max(w[j], 0.0));
+    for (int i = 0; i < d; ++i) at(x, i, j) = at(u, i, j) * r;
+    if (keep) keep[dd + j] = r;
+  }
+  if (keep) std::copy(u, u + dd, keep);
   for (int j = 0; j < d; ++j)
     for (int i = 0; i <= j; ++i) {
       double s = 0.0;
@@ -354,6 +363,20 @@ inline int qn_root(int d, double alpha, const double *g, const double *n_, doubl
     for (int i = 0; i < j; ++i) at(t, i, j) = at(t, j, i) = 0.5 * (at(t, i, j) + at(t, j, i));
   if (jacobi_eig(d, t, u, w) < 0) return -1;  // u = V, w = delta
   mul(x, u, a);                               // a = N P V
+  return 0;
+}
+
+// C (d x d, d = 2col, column-major, symmetric) and sum_i log1p(delta_i / alpha) from the Gram g = W'W and the
+// symmetric n_ of the model (both d x d).  work: 6 d^2 + d doubles.  Returns 0, -1 (the eigensolver did not
+// converge) or -2 (alpha + delta_i < -1e-8 alpha: the model is not positive definite).
+inline int qn_root(int d, double alpha, const double *g, const double *n_, double *cm, double *logsum, double *work) {
+  *logsum = 0.0;
+  if (d == 0) return 0;
+  const size_t dd = (size_t)d * d;
+  double *a = work, *u = work + dd, *w = work + 5 * dd, *nn = work + 5 * dd + d;
+  auto at = [d](double *m, int i, int j) -> double & { return m[i + (size_t)j * d]; };
+  double *ds = cm;  // (cm is written last: its first d entries hold D until then; C <- D^-1 C D^-1 at the end)
+  if (qn_spectrum(d, g, n_, ds, work, false) < 0) return -1;
   const double ra = std::sqrt(alpha);
   for (int i = 0; i < d; ++i) {
     if (alpha + w[i] < -1e-8 * alpha) return -2;
@@ -368,6 +391,166 @@ inline int qn_root(int d, double alpha, const double *g, const double *n_, doubl
       for (int k = 0; k < d; ++k) s = s + at(a, i, k) * w[k] * at(a, j, k);
       at(cm, i, j) = at(cm, j, i) = (at(nn, i, j) / (2.0 * ra) - s) / (u[i] * u[j]);
     }
+  return 0;
+}
+
+// ---- eigenvalues and eigenvectors of the model (lbfgsb_hip_qn_eig / qn_eigvec) ----
+// A = alpha I + W N W' has the eigenvalue alpha + delta_i with the unit eigenvector u_i = W (N P V)_i / delta_i for
+// every delta_i != 0 of qn_spectrum (|u_i|^2 = v_i'(P N P)^2 v_i / delta_i^2 = 1, and A u_i = alpha u_i + W N P
+// (P N P) v_i / delta_i), and alpha on the complement.  Directions with |delta_i| <= cut alpha belong to the bulk
+// eigenvalue alpha and are not returned.  *r directions remain; lam[0 .. r) = alpha + delta_i ascending (equal values
+// in the order of i); coef (d x r, column-major): column j holds the coefficients c of u in the unscaled [S, Y]
+// basis, its sign such that the entry of largest magnitude is positive (the first of equals).
+//
+// The coefficients.  (N P V)_i carries an absolute error of eps |N| |P|, so c = (N P V)_i / (delta_i D) loses what
+// delta_i is smaller than |N| |P|^2: a direction 1e-7 alpha off the bulk value keeps seven digits.  Since v_i lies in
+// the range of P, the same vector is u_i = W P^+ v_i, c = P^+ v_i / D, which costs the condition of P instead -- nothing
+// when the pairs are well separated, everything when two of them are nearly parallel, where the first form is exact to
+// rounding.  Both are formed, and a direction takes the second only where its own residual is below a quarter of the
+// first's (two residuals at the floor of their own rounding: the first form stays) -- the residual |W rho|, |W rho|^2
+// = rho'G rho with rho = N G c - delta_i c (A u - lambda u = W rho), plus the defect of the norm |delta_i| |c'G c - 1|,
+// measured on the scaled matrices: multiplications by G only, replicated host data, the same choice on every rank.
+// Many pairs of one run make the scaled G numerically singular (cond 1e16 at 33 pairs) and N as large as G is small:
+// then neither form resolves a direction to 1e-10 even at delta_i = 1e-2 alpha.  So every direction more than 100 cuts
+// off the bulk value takes one step of inverse iteration on M = N G, whose eigenvector for delta_i holds the
+// coefficients of u_i: delta_i is known to rounding, the step divides what the chosen form has of other directions
+// by their distance to delta_i, and it needs G as a matrix only (its absolute error, not its small eigenvalues).
+// Closer to the bulk value the step cannot tell the direction from the bulk (M's eigenvalue 0) and only adds its
+// own rounding to the norm: those directions stay as chosen.
+// W has rank <= rmax (its rows over all ranks): should more directions pass the cut, those of the smallest |delta|
+// go to the bulk as well.  lam: d doubles, coef: d^2 doubles, work: 7 d^2 + 6 d doubles.  Returns 0, -1 or -2 as
+// qn_root; *r = 0 then.
+inline int qn_eig(int d, double alpha, double cut, int64_t rmax, const double *g, const double *n_, int *r,
+                  double *lam, double *coef, double *work) {
+  *r = 0;
+  if (d == 0) return 0;
+  const size_t dd = (size_t)d * d;
+  const double *a = work, *v = work + dd, *w = work + 5 * dd, *nn = work + 5 * dd + d;
+  double *ds = work + 6 * dd + d, *keep = work + 6 * dd + 2 * d, *tmp = work + 7 * dd + 3 * d;
+  if (qn_spectrum(d, g, n_, ds, work, true, keep) < 0) return -1;
+  for (int i = 0; i < d; ++i)
+    if (alpha + w[i] < -1e-8 * alpha) return -2;
+  int idx[2 * 1024];
+  int cnt = 0;
+  for (int i = 0; i < d; ++i)
+    if (std::fabs(w[i]) > cut * alpha) idx[cnt++] = i;
+  while (cnt > rmax) {
+    int lo = 0;
+    for (int j = 1; j < cnt; ++j)
+      if (std::fabs(w[idx[j]]) < std::fabs(w[idx[lo]])) lo = j;
+    for (int j = lo; j + 1 < cnt; ++j) idx[j] = idx[j + 1];
+    --cnt;
+  }
+  std::stable_sort(idx, idx + cnt, [&](int x, int y) { return w[x] < w[y]; });
+  const double *ug = keep, *rg = keep + dd;  // the scaled G = ug diag(rg^2) ug'
+  double *c1 = tmp, *c2 = tmp + d, *t1 = tmp + 2 * d;
+  // the defect of a candidate c (scaled basis) for delta: sqrt(rho'G rho) + |c'G c - 1|, G and N the scaled ones
+  auto gmul = [&](const double *x, double *o) {  // o = G x through its factors
+    for (int k = 0; k < d; ++k) {
+      double s = 0.0;
+      for (int i = 0; i < d; ++i) s = s + ug[i + (size_t)k * d] * x[i];
+      t1[k] = s * (rg[k] * rg[k]);
+    }
+    for (int i = 0; i < d; ++i) {
+      double s = 0.0;
+      for (int k = 0; k < d; ++k) s = s + ug[i + (size_t)k * d] * t1[k];
+      o[i] = s;
+    }
+  };
+  std::vector<double> gc((size_t)d), rho((size_t)d), grho((size_t)d);
+  auto defect = [&](const double *c, double delta) {
+    gmul(c, gc.data());
+    double nrm = 0.0;
+    for (int i = 0; i < d; ++i) nrm = nrm + c[i] * gc[(size_t)i];
+    for (int i = 0; i < d; ++i) {
+      double s = 0.0;
+      for (int k = 0; k < d; ++k) s = s + nn[i + (size_t)k * d] * gc[(size_t)k];
+      rho[(size_t)i] = s - delta * c[i];
+    }
+    gmul(rho.data(), grho.data());
+    double q = 0.0;
+    for (int i = 0; i < d; ++i) q = q + rho[(size_t)i] * grho[(size_t)i];
+    return std::sqrt(std::max(q, 0.0)) + std::fabs(nrm - 1.0) * std::fabs(delta);
+  };
+  // One step of inverse iteration on M = N G (scaled; M c = delta c for the coefficients of an eigenvector, the bulk
+  // at M's eigenvalue 0) from the chosen form x: o = (M - delta I)^-1 x, scaled to o'G o = 1.  G here is the scaled
+  // Gram itself, not its clipped factors; LU with partial pivoting.  false, o undefined: a zero pivot or a result
+  // that is not finite.  (o may be x)
+  std::vector<double> gt(dd), mm(dd), lu(dd);
+  for (int q = 0; q < d; ++q)
+    for (int p = 0; p < d; ++p) gt[p + (size_t)q * d] = g[p + (size_t)q * d] / (ds[p] * ds[q]);
+  for (int q = 0; q < d; ++q)
+    for (int p = 0; p < d; ++p) {
+      double s = 0.0;
+      for (int k = 0; k < d; ++k) s = s + nn[p + (size_t)k * d] * gt[k + (size_t)q * d];
+      mm[p + (size_t)q * d] = s;
+    }
+  auto refine = [&](const double *x, double delta, double *o) {
+    lu = mm;
+    for (int p = 0; p < d; ++p) lu[p + (size_t)p * d] -= delta;
+    std::vector<double> b(x, x + d);
+    for (int k = 0; k < d; ++k) {
+      int piv = k;
+      for (int p = k + 1; p < d; ++p)
+        if (std::fabs(lu[p + (size_t)k * d]) > std::fabs(lu[piv + (size_t)k * d])) piv = p;
+      if (lu[piv + (size_t)k * d] == 0.0) return false;
+      if (piv != k) {
+        for (int q = 0; q < d; ++q) std::swap(lu[k + (size_t)q * d], lu[piv + (size_t)q * d]);
+        std::swap(b[(size_t)k], b[(size_t)piv]);
+      }
+      for (int p = k + 1; p < d; ++p) {
+        const double f = lu[p + (size_t)k * d] / lu[k + (size_t)k * d];
+        if (f == 0.0) continue;
+        for (int q = k + 1; q < d; ++q) lu[p + (size_t)q * d] -= f * lu[k + (size_t)q * d];
+        b[(size_t)p] -= f * b[(size_t)k];
+      }
+    }
+    for (int k = d - 1; k >= 0; --k) {
+      double s = b[(size_t)k];
+      for (int q = k + 1; q < d; ++q) s = s - lu[k + (size_t)q * d] * b[(size_t)q];
+      b[(size_t)k] = s / lu[k + (size_t)k * d];
+    }
+    double big = 0.0;  // (the solution is as long as the shift is close: scale before the norm)
+    for (int k = 0; k < d; ++k) big = std::max(big, std::fabs(b[(size_t)k]));
+    if (!(big > 0.0) || !std::isfinite(big)) return false;
+    for (int k = 0; k < d; ++k) b[(size_t)k] = b[(size_t)k] / big;
+    double nrm = 0.0;
+    for (int p = 0; p < d; ++p) {
+      double s = 0.0;
+      for (int q = 0; q < d; ++q) s = s + gt[p + (size_t)q * d] * b[(size_t)q];
+      nrm = nrm + b[(size_t)p] * s;
+    }
+    if (!(nrm > 0.0) || !std::isfinite(nrm)) return false;
+    nrm = std::sqrt(nrm);
+    for (int k = 0; k < d; ++k) o[k] = b[(size_t)k] / nrm;
+    return true;
+  };
+  for (int j = 0; j < cnt; ++j) {
+    const int i = idx[j];
+    lam[j] = alpha + w[i];
+    for (int k = 0; k < d; ++k) c1[k] = a[k + (size_t)i * d] / w[i];
+    for (int k = 0; k < d; ++k) {  // P^+ v_i = ug diag(1 / rg) ug' v_i over the kept directions
+      double s = 0.0;
+      for (int l = 0; l < d; ++l) s = s + ug[l + (size_t)k * d] * v[l + (size_t)i * d];
+      t1[k] = rg[k] > 0.0 ? s / rg[k] : 0.0;
+    }
+    for (int k = 0; k < d; ++k) {
+      double s = 0.0;
+      for (int l = 0; l < d; ++l) s = s + ug[k + (size_t)l * d] * t1[l];
+      c2[k] = s;
+    }
+    double *c = coef + (size_t)j * d;
+    const double *best = defect(c2, w[i]) < 0.25 * defect(c1, w[i]) ? c2 : c1;
+    if (std::fabs(w[i]) > 100.0 * cut * alpha && refine(best, w[i], c1)) best = c1;
+    int big = 0;
+    for (int k = 0; k < d; ++k) {
+      c[k] = best[k] / ds[k];
+      if (std::fabs(c[k]) > std::fabs(c[big])) big = k;
+    }
+    if (c[big] < 0.0)
+      for (int k = 0; k < d; ++k) c[k] = -c[k];
+  }
+  *r = cnt;
   return 0;
 }
 

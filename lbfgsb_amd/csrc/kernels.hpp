@@ -550,6 +550,14 @@ template <typename T>
 hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int col, const double *np, double alpha,
                           T *out);
 
+// The basis pass (k_qn_eig.hip): out_j (+)= [S, Y](:, tile) coef[j * 2 mc ...] for ALL j < k <= QN_BASIS_KMAX in one
+// launch, output j at out + j * ldo; the tile's columns are read once per row.  acc: add to what out holds (the tiles
+// after the first).  coef: DEVICE memory, 2 mc k doubles as qn_basis_pack lays them out, read through uniform (scalar)
+// loads.
+template <typename T>
+hipError_t launch_qn_basis(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, bool acc,
+                           const double *coef, int k, T *out, int64_t ldo);
+
 // Draws of the model (k_qn_draw.hip): the two passes above with the vectors generated, never loaded -- z_k[i] is the
 // N(0, 1) deviate of (seed, row0 + i, s0 + k) (philox.hpp).  k = 1, 2 or 4 (qn_kmax) samples from s0; s0 even
 // unless k = 1.

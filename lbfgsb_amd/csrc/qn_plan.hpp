@@ -95,4 +95,37 @@ inline void qn_pack_coef(const QnPiece &p, int col, const double *cf, double *co
   }
 }
 
+// ---- the basis pass (k_qn_eig.hip, lbfgsb_hip_qn_eigvec): OUT(n x k) = W(n x 2col) C(2col x k) ----
+// One launch per column tile writes ALL k <= QN_BASIS_KMAX outputs: the tiles are qn_plan's (from column 0, at most
+// QN_TILE pairs, capacity qn_mc), the first one stores its sums, every later one adds them to what is there (acc).
+// The coefficients of all tiles lie in one buffer, tile after tile: those of output j on a tile from off + j * 2 mc,
+// S(:, c0 + i) at + i and Y(:, c0 + i) at + mc + i, zero for the columns >= col (qn_pack_coef on a piece of k vectors).
+constexpr int QN_BASIS_KMAX = 128;
+struct QnBasisTile {
+  int c0, mc;
+  bool acc;
+  int off;  // of the tile's 2 mc k coefficients in the plan's buffer
+  constexpr QnPiece piece(int k) const { return QnPiece{c0, mc, 0, k, 0, QnCarry::None}; }
+};
+struct QnBasisPlan {
+  int col, k;
+  std::vector<QnBasisTile> tiles;
+  int total;  // coefficients of all tiles
+};
+// the coefficients a plan can need, for col <= max_col
+constexpr int qn_basis_coefs(int max_col) { return 2 * (max_col + QN_TILE) * QN_BASIS_KMAX; }
+inline QnBasisPlan qn_basis_plan(int col, int k) {
+  QnBasisPlan pl{col, k, {}, 0};
+  for (int c0 = 0; c0 < col; c0 += QN_TILE) {
+    const QnBasisTile t{c0, qn_mc(std::min(QN_TILE, col - c0)), c0 > 0, pl.total};
+    pl.tiles.push_back(t);
+    pl.total += 2 * t.mc * k;
+  }
+  return pl;
+}
+// cf[j * 2 col + i] (S part, then Y part) of the k outputs -> the plan's buffer
+inline void qn_basis_pack(const QnBasisPlan &pl, const double *cf, double *coef) {
+  for (const QnBasisTile &t : pl.tiles) qn_pack_coef(t.piece(pl.k), pl.col, cf, coef + t.off);
+}
+
 }  // namespace lbk

@@ -167,6 +167,8 @@ struct lbfgsb_hip_ctx {
                              void *out, int64_t ldo, double *h_logp) = 0;
   virtual int qn_vgram(int mode, int64_t k, const void *v, int64_t ldv, const void *center, double *h_g,
                        int64_t ldg) = 0;
+  virtual int qn_eig(int mode, int32_t cap, int32_t *h_r, double *h_bulk, double *h_lambda) = 0;
+  virtual int qn_eigvec(int mode, int64_t k, const int32_t *h_which, void *out, int64_t ldo) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

@@ -22,10 +22,19 @@
     int64_t gen = 0;            // pair generation: bumped by everything that changes W or col / head
     int64_t gram_gen = -1;      // generation of the Gram below
     std::vector<double> sty, yty;  // S'Y, Y'Y over all rows (col x col, logical order)
+    int64_t sts_gen = -1;          // generation of S'S below (qn_gram_ss: REAL32 contexts, the spectrum only)
+    std::vector<double> sts;       // S'S over all rows from the stored pairs
     int64_t n_gen[2] = {-1, -1};   // generation of the packed N of each mode (device copy in d_n[mode])
     int64_t root_gen[2] = {-1, -1};  // generation of the root of each mode below (qn_root_coef)
     std::vector<double> root_c[2];   // C of A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' (2col x 2col, column-major)
     double root_logsum[2] = {0.0, 0.0};  // sum_i log1p(delta_i / alpha): log det A - n log alpha
+    int64_t eig_gen[2] = {-1, -1};   // generation of the spectrum of each mode below (qn_eig_coef)
+    int eig_r[2] = {0, 0};           // directions off the bulk eigenvalue alpha
+    std::vector<double> eig_lam[2];  // their eigenvalues alpha + delta_i, ascending
+    std::vector<double> eig_c[2];    // their coefficient columns in the [S, Y] basis (2col x r, column-major)
+    bool basis = true;               // option "qn_basis": qn_eigvec by the basis pass (0: by qn_expand, 4 at a time)
+    std::vector<int64_t> coef_key;   // what d_coef holds: (generation, mode, k, the indices); empty: nothing
+    double *d_coef = nullptr, *h_coef = nullptr;  // the basis pass's coefficients and their pinned staging
     double *d_part = nullptr, *d_res = nullptr, *d_res_all = nullptr, *d_n[2] = {nullptr, nullptr};
     int all_ranks = 0;          // ranks d_res_all was sized for
     double *h_n = nullptr;      // pinned staging of a packed N
@@ -33,6 +42,7 @@
   } qn;
   static constexpr int QN_RES = lbk::qn_res(LBFGSB_MAX_M);                          // the sums of one vector block
   static constexpr int QN_NP = 64 * 65 / 2;                                         // packed N at 32 pairs
+  static constexpr int QN_COEFS = lbk::qn_basis_coefs(LBFGSB_QN_ROOT_MAXCOL);       // the basis pass's coefficients
 
   // save_locals: what the entries will read until the next return
   void qn_record(int col, int head, double theta, int iupdat) {
@@ -170,6 +180,26 @@
       qn.theta = qn.yty[(size_t)(col - 1) * (col + 1)] / sy[(size_t)(col - 1) * (m + 1)];
     return 0;
   }
+  // S'S over all rows from the stored pairs, once per pair generation, for the spectrum of a REAL32 context: the Ss
+  // the iteration keeps is summed from the steps before they are rounded into W, so it agrees with the stored fp32
+  // pairs to fp32 rounding only -- enough for B v, not for G = [S, Y]'[S, Y], whose error the coefficients of an
+  // eigenvector multiply by their square (unit vectors came out 2e-3 short).  fp64 contexts keep using Ss.
+  int qn_gram_ss() {
+    if (qn.sts_gen == qn.gen) return 0;
+    const int col = qn.col;
+    qn.sts.assign((size_t)col * col, 0.0);
+    std::vector<double> sums((size_t)2 * col * lbk::QN_KMAX);
+    for (int k0 = 0; k0 < col; k0 += lbk::QN_KMAX) {
+      const int kc = std::min(lbk::QN_KMAX, col - k0);
+      const T *v[lbk::QN_KMAX];
+      for (int kk = 0; kk < kc; ++kk) v[kk] = ws + (int64_t)((qn.head - 1 + k0 + kk) % m) * ld;
+      CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::None), v, true, nullptr, sums.data(), nullptr));
+      for (int kk = 0; kk < kc; ++kk)
+        for (int i = 0; i < col; ++i) qn.sts[i + (size_t)(k0 + kk) * col] = sums[(size_t)kk * 2 * col + i];
+    }
+    qn.sts_gen = qn.gen;
+    return 0;
+  }
   std::vector<double> qn_dg() const {
     std::vector<double> dg((size_t)qn.col);
     for (int i = 0; i < qn.col; ++i) dg[(size_t)i] = sy[(size_t)i * (m + 1)];
@@ -192,6 +222,25 @@
     };
   }
 
+  // N of the mode (as qn_diag forms it) and G = [S, Y]'[S, Y] from ss and the Gram (after qn_gram()), both 2col x 2col
+  // (sts: S'S from qn_gram_ss in place of Ss)
+  int qn_model_mats(bool inv, double *nm, double *g, const double *sts = nullptr) {
+    const int col = qn.col, d = 2 * col;
+    const int info = lbh::qn_nmat(col, qn_coef_map(inv), nm);
+    if (info) return info;
+    for (int j = 0; j < col; ++j)
+      for (int i = 0; i < col; ++i) {
+        g[i + (size_t)j * d] = sts ? sts[i + (size_t)j * col] : ss[(size_t)std::min(i, j) + (size_t)std::max(i, j) * m];
+        g[i + (size_t)(col + j) * d] = g[(col + j) + (size_t)i * d] = qn.sty[i + (size_t)j * col];
+        g[(col + i) + (size_t)(col + j) * d] = qn.yty[i + (size_t)j * col];
+      }
+    for (int j = 0; j < d; ++j)  // (Y'Y as the Gram pass summed it: symmetric up to rounding)
+      for (int i = 0; i < j; ++i) {
+        const double v = 0.5 * (g[i + (size_t)j * d] + g[j + (size_t)i * d]);
+        g[i + (size_t)j * d] = g[j + (size_t)i * d] = v;
+      }
+    return 0;
+  }
   // C of A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' and the log-det sum of B (inv = false) or H, once per pair
   // generation (host_dense.hpp, qn_root): G = [S, Y]'[S, Y] from ss and the Gram, N as qn_diag forms it
   int qn_root_coef(bool inv) {
@@ -201,19 +250,8 @@
     CHK(qn_gram());
     if (qn.root_gen[md] == qn.gen) return 0;
     std::vector<double> nm((size_t)d * d), g((size_t)d * d), work((size_t)6 * d * d + d);
-    const int info = lbh::qn_nmat(col, qn_coef_map(inv), nm.data());
+    const int info = qn_model_mats(inv, nm.data(), g.data());
     if (info) return info;
-    for (int j = 0; j < col; ++j)
-      for (int i = 0; i < col; ++i) {
-        g[i + (size_t)j * d] = ss[(size_t)std::min(i, j) + (size_t)std::max(i, j) * m];
-        g[i + (size_t)(col + j) * d] = g[(col + j) + (size_t)i * d] = qn.sty[i + (size_t)j * col];
-        g[(col + i) + (size_t)(col + j) * d] = qn.yty[i + (size_t)j * col];
-      }
-    for (int j = 0; j < d; ++j)  // (Y'Y as the Gram pass summed it: symmetric up to rounding)
-      for (int i = 0; i < j; ++i) {
-        const double v = 0.5 * (g[i + (size_t)j * d] + g[j + (size_t)i * d]);
-        g[i + (size_t)j * d] = g[j + (size_t)i * d] = v;
-      }
     qn.root_c[md].assign((size_t)d * d, 0.0);
     qn.root_gen[md] = -1;
     const int rc =
@@ -458,6 +496,96 @@
     }
     CHK(qn_launched(lbk::launch_qn_diag<T>(q, n, Wc(), qn.head, col, qn.d_n[md], qn_alpha(inv), (T *)out_),
                     "qn_diag"));
+    return qn_finish();
+  }
+  // The spectrum of B (inv = false) or H off the bulk eigenvalue alpha, once per pair generation (host_dense.hpp,
+  // qn_eig): the Gram pass and the host algebra of the root, no other pass over W
+  int qn_eig_coef(bool inv) {
+    const int col = qn.col, md = inv ? 1 : 0, d = 2 * col;
+    if (col > LBFGSB_QN_ROOT_MAXCOL) return fail(LBFGSB_E_ARG, "qn: the spectrum of more than 64 stored pairs");
+    if (col == 0) {
+      qn.eig_r[md] = 0;
+      return 0;
+    }
+    CHK(qn_gram());
+    if (qn.eig_gen[md] == qn.gen) return 0;
+    if (sizeof(T) == 4) CHK(qn_gram_ss());
+    std::vector<double> nm((size_t)d * d), g((size_t)d * d), work((size_t)7 * d * d + 6 * d);
+    const int info = qn_model_mats(inv, nm.data(), g.data(), sizeof(T) == 4 ? qn.sts.data() : nullptr);
+    if (info) return info;
+    qn.eig_lam[md].assign((size_t)d, 0.0), qn.eig_c[md].assign((size_t)d * d, 0.0);
+    qn.eig_gen[md] = -1;
+    const int rc = lbh::qn_eig(d, qn_alpha(inv), LBFGSB_QN_EIG_CUT, nglob, g.data(), nm.data(), &qn.eig_r[md],
+                               qn.eig_lam[md].data(), qn.eig_c[md].data(), work.data());
+    if (rc == -2) return fail(LBFGSB_E_STATE, "qn: the model is not positive definite");
+    if (rc) return fail(LBFGSB_E_STATE, "qn: the eigensolver of the spectrum did not converge");
+    qn.eig_gen[md] = qn.gen;
+    return 0;
+  }
+  int qn_eig(int mode, int32_t cap, int32_t *h_r, double *h_bulk, double *h_lambda) override {
+    CHK(qn_ready());
+    const bool inv = mode == LBFGSB_QN_H;
+    CHK(qn_eig_coef(inv));
+    const int r = qn.eig_r[inv ? 1 : 0];
+    *h_bulk = qn_alpha(inv), *h_r = r;
+    for (int i = 0; i < std::min<int>(r, cap); ++i) h_lambda[i] = qn.eig_lam[inv ? 1 : 0][(size_t)i];
+    return 0;
+  }
+  // out_j = the unit eigenvector number which[j] (NULL: j) of the mode: U = [S, Y] C, by one launch of the basis pass
+  // per column tile for all k outputs (qn_plan.hpp, qn_basis_plan), or, with the option "qn_basis" off, by qn_apply's
+  // expansion in blocks of QN_KMAX vectors with alpha = 0 (its src: a stored column of S, finite and never used)
+  int qn_eigvec(int mode, int64_t k_, const int32_t *which, void *out_, int64_t ldo) override {
+    CHK(qn_ready());
+    const bool inv = mode == LBFGSB_QN_H;
+    CHK(qn_eig_coef(inv));
+    const int col = qn.col, md = inv ? 1 : 0, d = 2 * col, k = (int)k_, r = qn.eig_r[md];
+    for (int j = 0; j < k; ++j)
+      if ((which ? which[j] : j) < 0 || (which ? which[j] : j) >= r)
+        return fail(LBFGSB_E_ARG, "qn_eigvec: an index outside 0 .. r - 1 (r of lbfgsb_hip_qn_eig)");
+    std::vector<double> cf((size_t)d * k);
+    for (int j = 0; j < k; ++j)
+      std::copy_n(qn.eig_c[md].data() + (size_t)(which ? which[j] : j) * d, d, cf.data() + (size_t)j * d);
+    const lbk::WStore<T> w = Wc();
+    T *out = (T *)out_;
+    if (!qn.basis) {
+      const T *any = ws + (int64_t)((qn.head - 1) % m) * ld;
+      for (int k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
+        const int kc = std::min(lbk::QN_KMAX, k - k0);
+        CHK(qn_expand_by(kc, cf.data() + (size_t)k0 * d, [&](const lbk::QnPiece &p, const double *coef) {
+          lbk::QnVecs<T> src{};
+          lbk::QnOuts<T> dst{};
+          for (int kk = 0; kk < p.k; ++kk) {
+            dst.p[kk] = out + (int64_t)(k0 + p.k0 + kk) * ldo;
+            src.p[kk] = p.c0 == 0 ? any : dst.p[kk];
+          }
+          return qn_launched(lbk::launch_qn_expand<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef,
+                                                      p.c0 == 0 ? 0.0 : 1.0, src, dst),
+                             "qn_expand");
+        }));
+      }
+      return qn_finish();
+    }
+    const lbk::QnBasisPlan pl = lbk::qn_basis_plan(col, k);
+    if (pl.total > QN_COEFS) return fail(LBFGSB_E_STATE, "qn: more coefficients than the buffer holds");
+    if (!qn.h_coef) {
+      HIPCHK(own.device(&qn.d_coef, (size_t)QN_COEFS * sizeof(double)));
+      HIPCHK(own.pinned(&qn.h_coef, (size_t)QN_COEFS * sizeof(double)));
+    }
+    // (the coefficients stay on the device while the pairs, the mode and the indices do: a repeated call neither
+    //  copies nor waits; a new set waits for the launches that may still read the old one, then for nothing)
+    std::vector<int64_t> key{qn.gen, (int64_t)md, (int64_t)k};
+    for (int j = 0; j < k; ++j) key.push_back(which ? which[j] : j);
+    if (key != qn.coef_key) {
+      qn.coef_key.clear();
+      HIPCHK(hipStreamSynchronize(stream));
+      lbk::qn_basis_pack(pl, cf.data(), qn.h_coef);
+      HIPCHK(hipMemcpyAsync(qn.d_coef, qn.h_coef, (size_t)pl.total * sizeof(double), hipMemcpyHostToDevice, stream));
+      qn.coef_key = key;
+    }
+    for (const lbk::QnBasisTile &t : pl.tiles)
+      CHK(qn_launched(lbk::launch_qn_basis<T>(q, n, w, qn.head, col, t.c0, t.mc, t.acc,
+                                              qn.d_coef + t.off, k, out, ldo),
+                      "qn_basis"));
     return qn_finish();
   }
   int qn_finish() {

@@ -49,6 +49,7 @@
       public :: lbfgsb_qn_logdet, lbfgsb_qn_draw       ! log det A and draws mean + scale A^(1/2) z, z ~ N(0, I)
       public :: lbfgsb_qn_quad, lbfgsb_qn_logpdf, lbfgsb_qn_draw_logpdf   ! d'A d and Gaussian log-densities
       public :: lbfgsb_qn_gram                          ! the k x k matrix (V - center)' A (V - center)
+      public :: lbfgsb_qn_eig, lbfgsb_qn_eigvec         ! eigenvalues and unit eigenvectors of B or H
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
                                                        ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
       ! slots of lbfgsb_kkt's cnt(:) and val(:): the header's LBFGSB_KKT_* indices + 1 (Fortran arrays start at 1)
@@ -191,6 +192,24 @@
             real(c_double) :: g(*)
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_gram
+         function lbfgsb_hip_qn_eig(ctx,mode,cap,r,bulk,lambda) bind(C,name='lbfgsb_hip_qn_eig') result(rc)
+            import :: c_int, c_int32_t, c_double, c_ptr
+            type(c_ptr),value :: ctx
+            integer(c_int),value :: mode
+            integer(c_int32_t),value :: cap
+            integer(c_int32_t) :: r
+            real(c_double) :: bulk
+            real(c_double) :: lambda(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_eig
+         function lbfgsb_hip_qn_eigvec(ctx,mode,k,which,out,ldo) bind(C,name='lbfgsb_hip_qn_eigvec') result(rc)
+            import :: c_int, c_int32_t, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, out
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, ldo
+            integer(c_int32_t) :: which(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_eigvec
          function lbfgsb_hip_qn_logpdf(ctx,mode,k,x,ldx,mean,scale,logp) bind(C,name='lbfgsb_hip_qn_logpdf') &
             result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
@@ -531,6 +550,37 @@
       rc = lbfgsb_hip_qn_gram(ctx, int(mode, c_int), int(k, c_int64_t), v, int(ldv, c_int64_t), center, g, &
                               int(ldg, c_int64_t))
       end subroutine lbfgsb_qn_gram
+
+      ! Eigenvalues and eigenvectors of the model (include/lbfgsb_hip.h, "Eigenvalues and eigenvectors"): A = bulk I +
+      ! U diag(lambda - bulk) U' with orthonormal U.  lbfgsb_qn_eig: bulk = theta (B) or 1 / theta (H), r the number
+      ! of eigenvalues off it, lambda(1 : min(r, cap)) those in ascending order (a host array of at least cap >= 1
+      ! entries; call with cap = 1 to learn r, at most 128).  lbfgsb_qn_eigvec: vector j = 1 .. k at out + (j - 1) ldo
+      ! is the unit eigenvector of eigenvalue number which(j), 1-BASED into that list (repeats allowed), k <= 128.
+      subroutine lbfgsb_qn_eig(ctx, mode, cap, r, bulk, lambda, rc)
+      type(c_ptr),intent(in) :: ctx
+      integer,intent(in) :: mode, cap
+      integer,intent(out) :: r
+      real(c_double),intent(out) :: bulk
+      real(c_double),intent(inout) :: lambda(*)
+      integer,intent(out) :: rc
+      integer(c_int32_t) :: r32
+      r32 = 0
+      rc = lbfgsb_hip_qn_eig(ctx, int(mode, c_int), int(cap, c_int32_t), r32, bulk, lambda)
+      r = int(r32)
+      end subroutine lbfgsb_qn_eig
+
+      subroutine lbfgsb_qn_eigvec(ctx, mode, k, which, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, out
+      integer,intent(in) :: mode, k, ldo
+      integer,intent(in) :: which(*)
+      integer,intent(out) :: rc
+      integer(c_int32_t) :: w0(128)
+      integer :: j
+      do j = 1, min(max(k, 0), 128)
+         w0(j) = int(which(j) - 1, c_int32_t)
+      end do
+      rc = lbfgsb_hip_qn_eigvec(ctx, int(mode, c_int), int(k, c_int64_t), w0, out, int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_eigvec
 
       subroutine lbfgsb_qn_logpdf(ctx, mode, k, x, ldx, mean, scale, logp, rc)
       type(c_ptr),intent(in) :: ctx, x, mean

@@ -465,6 +465,50 @@ class DeviceSolver:
                                           g.ctypes.data_as(C.POINTER(C.c_double)), k))
         return g
 
+    def qn_eig(self, inverse: bool = False):
+        """(bulk, values): the model A = B (inverse=False) or H is bulk I + U diag(values - bulk) U' with orthonormal
+        U -- bulk = theta or 1 / theta with multiplicity n_global - r, values a numpy (r,) array of the other
+        eigenvalues in ascending order, r <= min(2 col, n_global) (directions within capi.QN_EIG_CUT * bulk of the
+        bulk value count as bulk).  Host algebra on the Gram of the pairs alone: no pass over W beyond that Gram
+        pass, the same bits on every rank (collective on sharded contexts; at most 64 stored pairs)."""
+        r, bulk = C.c_int32(0), C.c_double(0.0)
+        mode = capi.QN_H if inverse else capi.QN_B
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_eig(self.h, mode, 0, C.byref(r), C.byref(bulk), None))
+        lam = np.zeros(r.value, np.float64)
+        if r.value:
+            check(self.lib.lbfgsb_hip_qn_eig(self.h, mode, r.value, C.byref(r), C.byref(bulk),
+                                             lam.ctypes.data_as(C.POINTER(C.c_double))))
+        return bulk.value, lam
+
+    def qn_eigvec(self, which=None, out=None, inverse: bool = False):
+        """The unit eigenvectors of B (inverse=False) or H as a (k, n) tensor of this rank's rows: row j belongs to
+        eigenvalue number which[j] of qn_eig's ascending list (repeats allowed; None: all r of them, or the first k of
+        an `out` of k rows).  One pass over the pairs per 16 of them writes all k <= 128 vectors.  Returns out."""
+        import torch
+        dt = torch.float32 if self.real == np.float32 else torch.float64
+        if which is None:
+            k = out.shape[0] if out is not None and out.dim() == 2 else (1 if out is not None else
+                                                                         len(self.qn_eig(inverse)[1]))
+            idx = None
+        else:
+            idx = np.ascontiguousarray(which, np.int32).reshape(-1)
+            k = int(idx.size)
+        if out is None:
+            out = torch.empty((k, self.n), dtype=dt, device=torch.device("cuda", self.device))
+            if k == 0:
+                return out
+        out = self._qn_vec(out, "out")
+        if (out.dim() == 1 and k != 1) or (out.dim() == 2 and out.shape[0] != k):
+            raise ValueError("out must have shape (k, n)")
+        ldo = self.n if out.dim() == 1 else out.stride(0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_eigvec(self.h, capi.QN_H if inverse else capi.QN_B, k,
+                                            None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            out.data_ptr(), ldo))
+        self._qn_done()
+        return out
+
     def qn_logpdf(self, x, mean=None, scale: float = 1.0, inverse: bool = True):
         """log N(x_j; mean, scale^2 A) over all rows of all ranks, the covariance A = H (inverse=True, as qn_draw's
         default) or B, for x of shape (n,) or (k, n): the quadratic form of A^-1 by qn_quad's pass and qn_logdet's
@@ -840,6 +884,28 @@ class QnOperator:
         if self.root:
             raise ValueError("gram() takes B or H, not a square root")
         return self.solver.qn_gram(v, center=center, inverse=self.inverse)
+
+    def _spectrum(self, what):
+        if self.root:
+            raise ValueError("%s takes B or H, not a square root" % what)
+        return self.solver.qn_eig(inverse=self.inverse)
+
+    def eigvalsh(self):
+        """(bulk, values) of DeviceSolver.qn_eig: the eigenvalues off the bulk value, ascending, as a numpy array"""
+        return self._spectrum("eigvalsh()")
+
+    def eigh(self):
+        """(bulk, values, vectors): A = bulk I + U diag(values - bulk) U', vectors a (r, n) tensor whose rows are the
+        orthonormal columns of U on this rank's rows (DeviceSolver.qn_eigvec)"""
+        bulk, values = self._spectrum("eigh()")
+        return bulk, values, self.solver.qn_eigvec(inverse=self.inverse)
+
+    def cond(self) -> float:
+        """the 2-norm condition number max / min over {bulk, values}, with no pass over W beyond the Gram pass (bulk is
+        an eigenvalue whenever n_global exceeds the number of values)"""
+        bulk, values = self._spectrum("cond()")
+        ev = list(values) + ([bulk] if self.solver.n_global > len(values) else [])
+        return float(max(ev) / min(ev))
 
     def log_prob(self, x, mean=None, scale: float = 1.0):
         """log N(x; mean, scale^2 A) with this operator as the covariance (DeviceSolver.qn_logpdf)"""
