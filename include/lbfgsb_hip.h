@@ -699,6 +699,7 @@ int lbfgsb_hip_objective(lbfgsb_hip_ctx *ctx, int kind, const void *x, void *g, 
  *                           pass runs as two launches over half of the columns each; 20 = three passes there)
  *   "lean" (0/1)            z and d = x - t left implicit by the storing pass
  *   "spec_capture" (0/1)    the update pass hands the next walk's first breakpoints over
+ *                           (not where one launch cannot for ALL rows: > 10 old pairs; "compact_w", > 5, n % 128 != 0)
  *   "pg_min" (count)        LBFGSB_F_PARALLEL_GCP: walks with more breakpoints in reach than this
  *                           go to the sort + scans
  *   "exact_always" (0/1)    every Cauchy walk in the reference's heap order from its start (tests)

@@ -386,6 +386,19 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
 // <= 8 values each and the nbd byte stream carries nbd | l-index << 2 | u-index << 5 (kernels_common.hpp).
 // cand_hi >= 0: rows whose breakpoint t lies in [0, cand_hi] are appended (unordered) to
 // ckeys / cidx (capacity ccap), *ccount = how many there are (zeroed by the launch)
+// Can ONE call of launch_update_scan hand the candidates over for ALL of its n rows?  (What the host asks before it
+// passes cand_hi >= 0: a list that misses rows is taken by the next walk for every breakpoint up to cand_hi.)  No
+//   * with the new-row sums at col - 1 > 10: the pair-shared MC = 20 instantiation has no registers for the
+//     hand-over, the split pass (col - 1 > Tune::split_from) runs its parts without it;
+//   * on the free-row layout (`layout`: the WStore carries lmask) with the new-row sums at 6 <= col - 1 <= 10 under
+//     Tune::pair_cw, when n >= CW_TILE is no multiple of CW_TILE: the pair-shared instantiation covers the whole
+//     tiles, the rows behind them are a launch of their own on offset pointers, which appends nothing.
+inline bool update_scan_hands_over(const Queue &q, int64_t n, int col, int newrow, bool layout) {
+  const int nold = col - 1;
+  if (newrow && (maxc_for(nold) > 10 || nold > q.tune.split_from)) return false;
+  if (layout && newrow && nold > 5 && nold <= 10 && q.tune.pair_cw && n >= CW_TILE && n % CW_TILE != 0) return false;
+  return true;
+}
 // Ws/Wy slot of logical column col-1 <- the pending pair (paths without a subspace pass)
 void launch_nbd_pack(Queue &q, int64_t n, const int32_t *nbd, nb_t *out);
 // Dictionary-coded bounds (ub bit 3 = UB_DICT, kernels_common.hpp): bound arrays with <= 8 distinct values each.

@@ -906,8 +906,9 @@ class Solver final : public lbfgsb_hip_ctx {
         const lbk::UpdScanSlots S{lbk::maxc_stride(c2 - 1), nr_flag(c2) != 0};
         clk_begin(1);
         q.res_off = fo;
-        // (the MC = 20 instantiation with the new-row sums has no registers for the hand-over)
-        const double chi = (nr_flag(c2) && lbk::maxc_for(c2 - 1) > 10) ? -1.0 : spec_hi(cnstnd);
+        // (only where the pass can hand over the candidates of ALL its rows: lbk::update_scan_hands_over)
+        const double chi =
+            lbk::update_scan_hands_over(q, n, c2, nr_flag(c2), Wc().lmask != nullptr) ? spec_hi(cnstnd) : -1.0;
         lbk::launch_update_scan<T>(q, n, x, lk(l), uk(u), nbk(), g, r, d_src(), d_impl ? 1 : 0, stp_here, iwhere,
                                    (T *)nullptr, Wc(), h2, c2, it2, 0, store_iw, nr_flag(c2), chi,
                                    sp_keys, sp_idx, SPEC_CAP, sp_count, ub_mask);
@@ -1656,7 +1657,8 @@ class Solver final : public lbfgsb_hip_ctx {
           lbk::launch_iwhere_update<T>(q, n, x, l, u, nbd, g, iwhere), iw_dirty += 1.0;  // the pass held it back
       } else {
         clk_begin(1);
-        const double chi = (nr_flag(col) && lbk::maxc_for(col - 1) > 10) ? -1.0 : spec_hi(cnstnd);
+        const double chi =
+            lbk::update_scan_hands_over(q, n, col, nr_flag(col), Wc().lmask != nullptr) ? spec_hi(cnstnd) : -1.0;
         lbk::launch_update_scan<T>(q, n, x, lk(l), uk(u), nbk(), g, r, d_src(), d_impl ? 1 : 0, stp, iwhere,
                                    (T *)nullptr, Wc(), head, col, itail, 0, 1, nr_flag(col), chi,
                                    sp_keys, sp_idx, SPEC_CAP, sp_count, ub_mask);

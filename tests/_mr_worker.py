@@ -28,6 +28,16 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     row0, n_loc = lbfgsb_amd.block_partition(n, world, rank)
+    options = {}
+    if variant == "symx":
+        options["exact_always"] = 1
+    elif os.environ.get("LBFGSB_TEST_COMPACT") == "1":
+        # the two passes over W on the tile-local free-row layout, re-sorted in every iteration
+        # (tests/test_gpu_compact.py)
+        options.update(compact_w=2, compact_policy=2)
+    if os.environ.get("LBFGSB_TEST_SPEC_CAPTURE") == "1":
+        options["spec_capture"] = 1      # the update pass hands the next walk's breakpoints over (tests/test_gpu_handover.py)
+
     def make_solver():
         s_ = lbfgsb_amd.DeviceSolver(n_loc, m, n_global=n, row0=row0, device=0,
                                      parallel_gcp=(variant in ("pgcp", "pgcp2")),
@@ -37,11 +47,7 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
                                      # (this worker evaluates f, g with sol.objective: the solver's own stream)
                                      same_stream_objective=os.environ.get("LBFGSB_TEST_DEFER") == "1",
                                      index_ties=(variant == "sym"),
-                                     options=({"exact_always": 1} if variant == "symx" else
-                                              # the two passes over W on the tile-local free-row layout, re-sorted in
-                                              # every iteration (tests/test_gpu_compact.py)
-                                              {"compact_w": 2, "compact_policy": 2}
-                                              if os.environ.get("LBFGSB_TEST_COMPACT") == "1" else None))
+                                     options=options or None)
         if mode == "gloo":
             lbfgsb_amd.attach_host_group(s_, rank, world)
         elif mode == "rccl1":
@@ -61,6 +67,12 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
         p, two_scale = two_scale_problem(po, n, m)
     elif variant in ("sym", "symx"):
         p, two_scale = symmetric_problem(po, n, m)
+    elif variant == "stair":
+        # the staircase case of tests/_handover_cases.py with this n and world: every rank's last n_loc % 128 rows bounded
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import _handover_cases as hc
+        case, = [c for c in hc.CASES if (c.n, c.m, c.world) == (n, m, world)]
+        p, two_scale = case.problem(po)
     elif variant == "rosen":
         p = po.problem_rosenbrock(n, m, factr=0.0, pgtol=0.0)
     else:
@@ -126,9 +138,11 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
     torch.cuda.synchronize()
     xs = [None] * world
     dist.all_gather_object(xs, x.cpu().numpy())
+    handed = [None] * world      # Cauchy walks served by the update pass's hand-over, per rank
+    dist.all_gather_object(handed, sol.path_counts()[2])
     if rank == 0:
         with open(out_path, "w") as fh:
-            json.dump({"rows": rows, "task": sol.task_s, "x": np.concatenate(xs).tolist(),
+            json.dump({"rows": rows, "task": sol.task_s, "x": np.concatenate(xs).tolist(), "handed": handed,
                        "stats": sol.stats(), "tie_splits": sol.tie_splits(), "defer": list(sol.defer_stats()),
                        "stopcpu": stopcpu if isinstance(stopcpu, bool) else None}, fh)
     sol.close()

@@ -349,6 +349,7 @@ def drive_with_replay(po, p, max_iter, pp=False, final_check=True, replay_all=Fa
         fgp, fo = float(sol.f[0]), float(so.f[0])
         LAST["stats"] = sol.stats()
         LAST["tie_splits"] = sol.tie_splits()
+        LAST["path_counts"] = sol.path_counts()
     finally:
         sol.close()
     LAST.update(f_oracle=fo, f_gpu=fgp, task_oracle=so.task_s, task_gpu=rg[-1][0], calls_gpu=len(rg))
@@ -387,7 +388,12 @@ def drive_with_replay(po, p, max_iter, pp=False, final_check=True, replay_all=Fa
     # the two passes over W on the tile-local free-row layout (m <= 10), the tiles re-sorted in every iteration and
     # un-sorted by every export of the replay harness; and packed by the automatic rule
     (9200, 60, 400, 1, 11, "compact_w=2,compact_policy=2"), (9300, 40, 3000, 1, 11, "pp,compact_w=2,compact_policy=2"),
-    (9400, 40, 3000, 3, 11, "pp,compact_w=1,compact_min_rows=0")])
+    (9400, 40, 3000, 3, 11, "pp,compact_w=1,compact_min_rows=0"),
+    # the hand-over together with the layout (n mostly not a multiple of the tile: the rows behind the last whole tile
+    # are a launch of their own at col - 1 >= 6), and on the natural-order instantiations without the new-row sums
+    # (constructed inputs whose walks ARE served: tests/test_gpu_handover.py)
+    (9600, 40, 400, 7, 11, "spec_capture=1,compact_w=2,compact_policy=2"),
+    (9700, 30, 1500, 11, 33, "pp,spec_capture=1,two_pass=0")])
 def test_random_problems_against_oracle(oracle_built, first, count, nmax, mlo, mhi, switch):
     po = oracle_built
     words = switch.split(",") if switch else []

@@ -1340,7 +1340,10 @@ def test_device_path_to_convergence_against_oracle(env, n, m, mixed, min_agree, 
     columns (iteration, nfg, nseg, nfree) equal the oracle's for at least `min_agree` iterations
     (all 72 of the n = 1000 fixture; beyond that the stop test acts on rounding noise), f agrees
     to 1e-11 throughout, same final message.  `handover`: with the option spec_capture = 1 the update
-    pass also hands the next walk's first breakpoints over (off by default: DESIGN.md section 4)."""
+    pass also hands the next walk's first breakpoints over (off by default: DESIGN.md section 4), and walks must
+    have been served by it: at least 2 at n = 4096, 1 at n = 100003 (a CPU model of the host's rule -- spec_hi and
+    window_fetch in solver_provider.inl -- predicts 8 and 2).  For n = 1000 the same model predicts NONE, so no floor is asserted
+    there: the walks that ARE served at small n are those of tests/test_gpu_handover.py."""
     po, torch, la = env["po"], env["torch"], env["la"]
     p = po.problem_quadratic(n, m, mixed_nbd=mixed)
     rows_o = []
@@ -1365,7 +1368,11 @@ def test_device_path_to_convergence_against_oracle(env, n, m, mixed, min_agree, 
             break
     handed = sol.path_counts()[2]
     sol.close()
-    assert handed == 0 if not handover else handed >= 0
+    print("n = %d: %d walks served by the hand-over" % (n, handed))
+    if not handover:
+        assert handed == 0
+    else:
+        assert handed >= {1000: 0, 4096: 2, 100003: 1}[n], handed       # observed: 0, 8, 2
     assert t == so.task_s and t.startswith("CONVERGENCE")
     k = 0
     while k < min(len(rows_o), len(rows_g)) and rows_o[k][:4] == rows_g[k][:4]:
