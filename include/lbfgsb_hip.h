@@ -734,6 +734,10 @@ int lbfgsb_hip_objective(lbfgsb_hip_ctx *ctx, int kind, const void *x, void *g, 
  *   "wide_incr" (0/1)       m > 32: formk adds the new pair's row and column to WN1 while no row changes status
  *                           (default 1) / from scratch whenever it runs
  *   "nt" (0/1)              nontemporal loads in the passes over W (default: by the size of W)
+ *   "cw_dense" (0/1)        "compact_w": the storing pass and the lane-pair update pass (m = 10, > 5 pairs) fetch a
+ *                           tile's run of layout-free entries of each stored column by 16-byte loads and hand them to
+ *                           the lanes that own the rows through LDS (default 1) / two 8-byte loads per column in which
+ *                           every lane takes part: the same values, the same sums, bit for bit
  *   "qn_basis" (0/1)        qn_eigvec writes all its vectors in one pass over W per tile of 16 pairs (default 1) / goes
  *                           through qn_apply's expansion, 4 vectors a pass: the same products summed in another order
  *   "uniform_bounds" (0/1)  detect bound arrays that hold one value each (lbfgsb_hip_uniform_bounds)

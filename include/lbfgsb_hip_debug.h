@@ -74,6 +74,9 @@ int lbfgsb_hip_host_gap(lbfgsb_hip_ctx *ctx, double *seconds, int64_t *count);
  * the layout (fp64, m <= 10, no LBFGSB_F_MIRROR_INDEX, option set). */
 int lbfgsb_hip_compact_stats(lbfgsb_hip_ctx *ctx, int64_t *packs, int64_t *unpacks, int32_t *packed,
                              int32_t *eligible);
+/* Option "cw_dense": how often this context launched the storing pass's and the update pass's kernel with the dense
+ * run loads (0 under cw_dense = 0, and for the shapes that have no such kernel: the update pass up to 5 pairs). */
+int lbfgsb_hip_dense_launches(lbfgsb_hip_ctx *ctx, int64_t *storing, int64_t *update);
 /* ONE host sync of the iteration timed by itself, `reps` times (microseconds: median and minimum): the
  * 8 min(m, 32) + 15 fp64 partials of the widest phase through the library's own fetch -- with a communicator the
  * all-gather over the ranks on the solver's stream (the sums of src/lbfgsb.f90:813-816, 2196-2244

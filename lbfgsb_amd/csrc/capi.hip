@@ -539,6 +539,15 @@ int lbfgsb_hip_compact_stats(lbfgsb_hip_ctx *ctx, int64_t *packs, int64_t *unpac
   return 0;
 }
 
+int lbfgsb_hip_dense_launches(lbfgsb_hip_ctx *ctx, int64_t *storing, int64_t *update) {
+  if (!ctx) return fail(LBFGSB_E_ARG, "ctx == NULL");
+  int64_t a = 0, b = 0;
+  ctx->dense_launches(a, b);
+  if (storing) *storing = a;
+  if (update) *update = b;
+  return 0;
+}
+
 int lbfgsb_hip_refresh_count(lbfgsb_hip_ctx *ctx, int64_t *count) {
   if (!ctx || !count) return fail(LBFGSB_E_ARG, "refresh_count: NULL argument");
   *count = ctx->nrefresh;

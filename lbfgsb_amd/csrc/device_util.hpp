@@ -495,11 +495,18 @@ __device__ __forceinline__ void cw_slots(const CwTile &t, int (&sl)[2], bool (&l
   sl[0] = lf[0] ? b0 : tf + (lane - b0);
   sl[1] = lf[1] ? b1 : tf + (64 + lane - b1);
 }
+// between LDS accesses of one wave that hand data from lane to lane.  For the COMPILER, which otherwise reorders a
+// lane's write and its reads at other places (measured: wrong entries without it); the hardware needs nothing, the
+// LDS operations of a wave complete in the order they were issued, and the fence costs no instruction
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
 __device__ __forceinline__ int64_t wave_uniform(int64_t v) {
   return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
                    (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
 }
-// Trip2: issue_cw(const Ctx &, const CwTile &), land();  f(trip, first row of the tile, WTag<2>)
+// Trip2: issue_cw(const Ctx &, const CwTile &), land_cw(const Ctx &);  f(trip, first row of the tile, WTag<2>)
 // Trip1: issue_cw(const Ctx &, int64_t i, int64_t slot, bool lf, int64_t tile_first), land();  f(trip, i, WTag<1>)
 template <typename Trip2, typename Trip1, typename Ctx, typename F>
 __device__ __forceinline__ void for_tiles_cw(int64_t n, const Ctx &c, const uint64_t *__restrict__ lmask, F &&f) {
@@ -520,7 +527,7 @@ __device__ __forceinline__ void for_tiles_cw(int64_t n, const Ctx &c, const uint
       Trip2 A;
       A.issue_cw(c, CwTile{tr << 7, m0, m1});
       raw_wait<0>();
-      A.land();
+      A.land_cw(c);
       f(A, tr << 7, WTag<2>{});
       if (!more) break;
       tr = nx, m0 = m0n, m1 = m1n;
@@ -548,7 +555,8 @@ __device__ __forceinline__ void for_tiles_cw(int64_t n, const Ctx &c, const uint
 // The same layout walked in HALF tiles: a wave takes 64 rows per trip, lane l owns row l of the half -- one row per
 // lane and trip, as the natural-order kernels with many accumulators run (RowsPerAcc): the update pass with formk's
 // new-row sums, whose lane pairs share the column accumulators (UpdScanPairTripCW) and so keep two waves per SIMD.
-// Trip1 as above; f(trip, i, WTag<1>).  The partial half behind the full ones is taken by itself.
+// Trip1 as above (+ static constexpr bool DENSE, land_cw(const Ctx &) and, where DENSE, issue_cw_run);
+// f(trip, i, WTag<1>).  The partial half behind the full ones is taken by itself.
 template <typename Trip1, typename Ctx, typename F>
 __device__ __forceinline__ void for_halves_cw(int64_t n, const Ctx &c, const uint64_t *__restrict__ lmask, F &&f) {
   const int lane = threadIdx.x & 63;
@@ -556,7 +564,9 @@ __device__ __forceinline__ void for_halves_cw(int64_t n, const Ctx &c, const uin
   const int64_t stride = (int64_t)gridDim.x * (blockDim.x >> 6);
   const int64_t t0 = wave_uniform((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   // start every load of half h (its tile's mask words m0, m1 are wave-uniform)
-  auto issue = [&](Trip1 &A, int64_t h, uint64_t m0, uint64_t m1, int64_t row_limit) {
+  // (`full`: a full half -- a trip type with DENSE may fetch the half's run [c0 or 0, tf or c0) of each column by
+  //  16-byte loads, issue_cw_run; the partial half is always taken by today's loads)
+  auto issue = [&](Trip1 &A, int64_t h, uint64_t m0, uint64_t m1, int64_t row_limit, bool full) {
     const bool hi = (h & 1) != 0;  // (uniform)
     const int c0 = __popcll(m0), tf = c0 + __popcll(m1);
     const uint64_t mw = hi ? m1 : m0;
@@ -567,6 +577,12 @@ __device__ __forceinline__ void for_halves_cw(int64_t n, const Ctx &c, const uin
     const int64_t tb = (h >> 1) << 7;
     int64_t i = (h << 6) + lane;
     if (i >= row_limit) i = row_limit - 1;
+    if constexpr (Trip1::DENSE) {
+      if (full) {
+        A.issue_cw_run(c, i, tb + (lf ? b : tf + (r - b)), lf, tb, hi ? c0 : 0, hi ? tf : c0);
+        return;
+      }
+    }
     A.issue_cw(c, i, tb + (lf ? b : tf + (r - b)), lf, tb);
   };
   if (t0 < nh) {
@@ -577,9 +593,9 @@ __device__ __forceinline__ void for_halves_cw(int64_t n, const Ctx &c, const uin
       const int64_t nx = h + stride, nxc = cl(nx);
       const uint64_t m0n = lmask[(nxc >> 1) * 2], m1n = lmask[(nxc >> 1) * 2 + 1];  // the next trip's words
       Trip1 A;
-      issue(A, h, m0, m1, n);
+      issue(A, h, m0, m1, n, true);
       raw_wait<0>();
-      A.land();
+      A.land_cw(c);
       f(A, (h << 6) + lane, WTag<1>{});
       if (nx >= nh) break;
       h = nx, m0 = m0n, m1 = m1n;
@@ -588,9 +604,9 @@ __device__ __forceinline__ void for_halves_cw(int64_t n, const Ctx &c, const uin
   if ((n & 63) != 0 && t0 == nh % stride) {  // the partial half
     const uint64_t m0 = lmask[(nh >> 1) * 2], m1 = lmask[(nh >> 1) * 2 + 1];
     Trip1 A;
-    issue(A, nh, m0, m1, n);
+    issue(A, nh, m0, m1, n, false);
     raw_wait<0>();
-    A.land();
+    A.land_cw(c);
     if ((nh << 6) + lane < n) f(A, (nh << 6) + lane, WTag<1>{});
   }
 }

@@ -40,6 +40,7 @@ struct SubsmCtx {
   int m, head, col;
   Pend pe;
   int ub;  // uniform bounds: bit 0 l, bit 1 u, bit 2 nbd are 64-byte constant buffers (see UpdScanCtx)
+  i32x4_t *scr = nullptr;  // DN (SubsmTripCW2): the workgroup's LDS scratch, 2 KiB per wave
 };
 template <typename T, int MC, int W>
 struct SubsmRegs {  // the register images of one row group
@@ -117,7 +118,14 @@ struct SubsmTripCW1 : SubsmRegs<T, MC, 1>, CwOneRow {
   __device__ __forceinline__ void land() {}
 };
 // ... the rows lane, lane + 64 of a full tile as one row group of width 2 (see UpdScanTripCW2, k_update.hip)
-template <typename T, int MC, bool NT, bool PSPEC>
+// DN (option "cw_dense"): a tile's layout-free entries of a stored column are ONE contiguous run, [tile, tile + tf).
+// Instead of two 8-byte loads in which every lane takes part -- the lanes whose row has no bit re-reading the tile's
+// first entry -- each column is fetched by one 16-byte load of that run (lane l: slots 2l, 2l + 1; the lanes with
+// 2l >= tf are off) and handed to the lanes that own the rows through LDS after the wait, column pair by column pair:
+// one 16-byte write per lane, then an 8-byte read at each of the lane's two slots.  Half the load instructions for
+// the same bytes; what a row without a bit gets, nothing in the storing pass looks at.  When tf is odd the last
+// active lane reads one slot past the run: an entry of the same tile.
+template <typename T, int MC, bool NT, bool PSPEC, bool DN = false>
 struct SubsmTripCW2 : SubsmRegs<T, MC, 2>, CwPairRows {
   static_assert(sizeof(T) == 8, "compact W: fp64");
   static constexpr int NL = 2 * (6 + 2 * MC);
@@ -160,6 +168,26 @@ struct SubsmTripCW2 : SubsmRegs<T, MC, 2>, CwPairRows {
           }
       }
     }
+    if constexpr (DN) {
+      const int tf = __popcll(t.m0) + __popcll(t.m1);
+      // (unroll slots beyond the stored pairs: what the zero buffer holds)
+#pragma unroll
+      for (int j = 0; j < (PSPEC ? MC - 1 : MC); ++j)
+        if (!PSPEC && j >= c.col) this->ra[j].v = i32x4_t{0, 0, 0, 0}, this->rb[j].v = i32x4_t{0, 0, 0, 0};
+      // (loads inside a divergent branch, their first use behind the join: raw_issue is an ORDINARY load, not inline
+      //  asm -- the compiler sees the destination as in flight and puts its s_waitcnt in front of whatever it
+      //  places at the join, a copy included; device_util.hpp, "loads the kernel schedules itself")
+      if (2 * lane < tf) {
+#pragma unroll
+        for (int j = 0; j < (PSPEC ? MC - 1 : MC); ++j)
+          if (stored_col(c, j)) {
+            const int64_t off = (PSPEC ? (int64_t)((c.head - 1 + j) % c.m) * c.ldw : col_off(j, c.col, c.head, c.m, c.ldw)) + t.tb + 2 * lane;
+            raw_issue<16, false>(this->ra[j], c.wy + off);
+            raw_issue<16, false>(this->rb[j], c.ws + off);
+          }
+      }
+      return;
+    }
     int sl[2];
     bool lf[2];
     cw_slots(t, sl, lf);
@@ -170,29 +198,64 @@ struct SubsmTripCW2 : SubsmRegs<T, MC, 2>, CwPairRows {
     cols_row<false>(c, 0, t.tb + (lf[0] ? sl[0] : 0));
     cols_row<false>(c, 1, t.tb + (lf[1] ? sl[1] : 0));
   }
-  __device__ __forceinline__ void land() {
+  // a column that lives in W (not the pending pair's, not an unroll slot beyond the pairs)
+  __device__ __forceinline__ static bool stored_col(const SubsmCtx<T> &c, int j) {
+    return PSPEC || (j < c.col && !(c.pe.on && j == c.col - 1));
+  }
+  __device__ __forceinline__ void land_cw(const SubsmCtx<T> &c) {
     raw_join_bytes(this->rnb, nb_[0], nb_[1]);
     raw_join_bytes(this->riw, iw_[0], iw_[1]);
+    if constexpr (DN) {
+      const int lane = (int)(threadIdx.x & 63);
+      int sl[2];
+      bool lf[2];
+      cw_slots(this->tile_, sl, lf);
+      const bool act = 2 * lane < __popcll(this->tile_.m0) + __popcll(this->tile_.m1);
+      // this wave's two column tiles (Wy, Ws).  LDS operations of one wave complete in the order they were issued
+      // (wave_lds_order): no wait between a column's reads and the next column's writes, and the reads land in the
+      // image the write has just consumed.  A row without a bit reads slot 0 -- the tile's first entry, as the plain loads
+      // do, or, in a tile without a free row, whatever an earlier column left there (the scratch starts as zeros):
+      // nothing in this pass looks at it.
+      i32x4_t *wa = c.scr + (threadIdx.x >> 6) * 128, *wb = wa + 64;
+      const i32x2_t *pa = reinterpret_cast<const i32x2_t *>(wa), *pb = reinterpret_cast<const i32x2_t *>(wb);
+      const int d0 = lf[0] ? sl[0] : 0, d1 = lf[1] ? sl[1] : 0;
+#pragma unroll
+      for (int j = 0; j < (PSPEC ? MC - 1 : MC); ++j)
+        if (stored_col(c, j)) {
+          if (act) wa[lane] = this->ra[j].v, wb[lane] = this->rb[j].v;
+          wave_lds_order();
+          this->ra[j].v.xy = pa[d0], this->ra[j].v.zw = pa[d1];
+          this->rb[j].v.xy = pb[d0], this->rb[j].v.zw = pb[d1];
+          wave_lds_order();
+        }
+    }
   }
 };
-// CW: W in the tile-local free-row layout `lmask` (fp64, MC <= 10; for_tiles_cw)
-template <typename T, int MC, bool NT, bool PSPEC, bool PIPE, bool CW = false>
-__global__ __launch_bounds__(BLOCK) void subsm_update_kernel(
+// CW: W in the tile-local free-row layout `lmask` (fp64, MC <= 10; for_tiles_cw); DN: SubsmTripCW2's dense loads
+// (the kernels proper follow the body: subsm_update_kernel, subsm_update_kernel_dense)
+template <typename T, int MC, bool NT, bool PSPEC, bool PIPE, bool CW, bool DN>
+__device__ __forceinline__ void subsm_update_body(
     int64_t n, double tsum, T *__restrict__ zout, const T *pr, T *rout,
     const T *__restrict__ l, const T *__restrict__ u, const nb_t *__restrict__ nbd,
     const iw_t *__restrict__ iwhere, const T *xx, const T *__restrict__ gg,
     const T *__restrict__ ws, const T *__restrict__ wy, const T *__restrict__ zero, int64_t ldw,
     int m, int head, int col, double theta, Coef cf, Coef wv, T *dvec, T *tvec,
     T *xout, int do_stpmx, Pend pe, const T *pd, T *cwy, T *cws, int ub, double *part, int pstride,
-    const uint64_t *__restrict__ lmask = nullptr) {
+    const uint64_t *__restrict__ lmask) {
   static_assert(!CW || (sizeof(T) == 8 && MC <= 10 && !PIPE), "compact W: fp64, MC <= 10, one trip in flight");
+  static_assert(CW || !DN, "dense loads: the layout's instantiations");
   double acc[SUBSM_SIZE] = {0.0, 0.0, 0.0, 1.0e10};  // (SubsmSlot: three sums, the minimum)
   const double rtheta = 1.0 / theta;
   constexpr int V = RowsPer<T, MC>::V;
   // stores every trip issues (a lower bound: the counted wait of the pipelined loop may then wait
   // for a few stores too): the trial point / z (+ the committed pair in the steady-state shape)
   constexpr int NS = PSPEC ? 3 : 1;
-  const SubsmCtx<T> ctx{l, u, xx, gg, ws, wy, zero, pr, pd, nbd, iwhere, ldw, m, head, col, pe, ub};
+  __shared__ i32x4_t cw_scr[DN ? (BLOCK / 64) * 128 : 1];
+  if constexpr (DN) {  // (every wave its own 2 KiB: no barrier)
+    i32x4_t *own = cw_scr + (threadIdx.x >> 6) * 128 + (threadIdx.x & 63);
+    own[0] = i32x4_t{0, 0, 0, 0}, own[64] = i32x4_t{0, 0, 0, 0};
+  }
+  const SubsmCtx<T> ctx{l, u, xx, gg, ws, wy, zero, pr, pd, nbd, iwhere, ldw, m, head, col, pe, ub, cw_scr};
   __shared__ T dict[16];
   dict_fill<T>(dict, l, u, ub);
   auto body = [&](auto &tr, int64_t i, auto wt) {
@@ -284,10 +347,37 @@ __global__ __launch_bounds__(BLOCK) void subsm_update_kernel(
     if (xout) tr.template st_rows<NT>(xout, i, zv);
   };
   if constexpr (CW)
-    for_tiles_cw<SubsmTripCW2<T, MC, NT, PSPEC>, SubsmTripCW1<T, MC, NT, PSPEC>>(n, ctx, lmask, body);
+    for_tiles_cw<SubsmTripCW2<T, MC, NT, PSPEC, DN>, SubsmTripCW1<T, MC, NT, PSPEC>>(n, ctx, lmask, body);
   else
     for_rows_raw<SubsmTrip<T, MC, V, NT, PSPEC>, SubsmTrip<T, MC, 1, NT, PSPEC>, V, PIPE, NS>(n, ctx, body);
   block_reduce_store<SUBSM_SIZE>(acc, SUBSM_NSUM, 1, 0, part, pstride);
+}
+template <typename T, int MC, bool NT, bool PSPEC, bool PIPE, bool CW = false>
+__global__ __launch_bounds__(BLOCK) void subsm_update_kernel(
+    int64_t n, double tsum, T *__restrict__ zout, const T *pr, T *rout,
+    const T *__restrict__ l, const T *__restrict__ u, const nb_t *__restrict__ nbd,
+    const iw_t *__restrict__ iwhere, const T *xx, const T *__restrict__ gg,
+    const T *__restrict__ ws, const T *__restrict__ wy, const T *__restrict__ zero, int64_t ldw,
+    int m, int head, int col, double theta, Coef cf, Coef wv, T *dvec, T *tvec,
+    T *xout, int do_stpmx, Pend pe, const T *pd, T *cwy, T *cws, int ub, double *part, int pstride,
+    const uint64_t *__restrict__ lmask = nullptr) {
+  subsm_update_body<T, MC, NT, PSPEC, PIPE, CW, false>(
+      n, tsum, zout, pr, rout, l, u, nbd, iwhere, xx, gg, ws, wy, zero, ldw, m, head, col, theta, cf, wv, dvec, tvec, xout,
+      do_stpmx, pe, pd, cwy, cws, ub, part, pstride, lmask);
+}
+// ... on the layout with SubsmTripCW2's dense loads (option "cw_dense")
+template <typename T, int MC, bool NT, bool PSPEC>
+__global__ __launch_bounds__(BLOCK) void subsm_update_kernel_dense(
+    int64_t n, double tsum, T *__restrict__ zout, const T *pr, T *rout,
+    const T *__restrict__ l, const T *__restrict__ u, const nb_t *__restrict__ nbd,
+    const iw_t *__restrict__ iwhere, const T *xx, const T *__restrict__ gg,
+    const T *__restrict__ ws, const T *__restrict__ wy, const T *__restrict__ zero, int64_t ldw,
+    int m, int head, int col, double theta, Coef cf, Coef wv, T *dvec, T *tvec,
+    T *xout, int do_stpmx, Pend pe, const T *pd, T *cwy, T *cws, int ub, double *part, int pstride,
+    const uint64_t *__restrict__ lmask) {
+  subsm_update_body<T, MC, NT, PSPEC, false, true, true>(
+      n, tsum, zout, pr, rout, l, u, nbd, iwhere, xx, gg, ws, wy, zero, ldw, m, head, col, theta, cf, wv, dvec, tvec, xout,
+      do_stpmx, pe, pd, cwy, cws, ub, part, pstride, lmask);
 }
 template <typename T>
 void launch_subsm_update(Queue &q, int64_t n, double tsum, T *zout, const T *pr, T *rout, const T *l,
@@ -304,14 +394,17 @@ void launch_subsm_update(Queue &q, int64_t n, double tsum, T *zout, const T *pr,
     bool done = false;
     if constexpr (sizeof(T) == 8) {
       if (col <= 10) {
-#define LB_SUBSM_CW(MCV, NTV, PSPECV)                                                                           \
-  {                                                                                                             \
-    gr = grid_for_w(q, n, VecOf<T>::V, (const void *)&subsm_update_kernel<T, MCV, NTV, PSPECV, false, true>);   \
-    hipLaunchKernelGGL((subsm_update_kernel<T, MCV, NTV, PSPECV, false, true>), dim3(gr), dim3(BLOCK), 0,       \
-                       q.stream, n, tsum, zout, pr, rout, l, u, nbd, iwhere, xx, gg, w.ws, w.wy, w.zero, w.ld,   \
-                       w.m, head, col, theta, cf, wv, dvec, tvec, xout, do_stpmx, pe, pd, w.wy + slot,          \
-                       w.ws + slot, ub, part, pstride, w.lmask);                                                \
+#define LB_SUBSM_CW_(...)                                                                                      \
+  {                                                                                                           \
+    gr = grid_for_w(q, n, VecOf<T>::V, (const void *)&__VA_ARGS__);                                                  \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3(gr), dim3(BLOCK), 0,                                                      \
+                       q.stream, n, tsum, zout, pr, rout, l, u, nbd, iwhere, xx, gg, w.ws, w.wy, w.zero, w.ld, \
+                       w.m, head, col, theta, cf, wv, dvec, tvec, xout, do_stpmx, pe, pd, w.wy + slot,        \
+                       w.ws + slot, ub, part, pstride, w.lmask);                                              \
   }
+#define LB_SUBSM_CW(MCV, NTV, PSPECV) \
+  { if (q.cw_dense) { q.n_dense_subsm++; LB_SUBSM_CW_(subsm_update_kernel_dense<T, MCV, NTV, PSPECV>) } \
+    else LB_SUBSM_CW_(subsm_update_kernel<T, MCV, NTV, PSPECV, false, true>) }
         if (col <= 5) {
           if (q.nt) { if (spec) LB_SUBSM_CW(5, true, true) else LB_SUBSM_CW(5, true, false) }
           else { if (spec) LB_SUBSM_CW(5, false, true) else LB_SUBSM_CW(5, false, false) }
@@ -320,6 +413,7 @@ void launch_subsm_update(Queue &q, int64_t n, double tsum, T *zout, const T *pr,
           else { if (spec) LB_SUBSM_CW(10, false, true) else LB_SUBSM_CW(10, false, false) }
         }
 #undef LB_SUBSM_CW
+#undef LB_SUBSM_CW_
         LB_LAUNCHED(q);
         finalize_from(q, part, pstride, gr, SUBSM_NSUM, 1, 0);
         done = true;

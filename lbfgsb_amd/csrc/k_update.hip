@@ -99,6 +99,7 @@ struct UpdScanCtx {
   int ub;
   // PAIR: column pointers per lane parity, in LDS (see UpdScanPairTrip)
   const unsigned long long *ptab;
+  i32x4_t *scr = nullptr;  // DN (UpdScanPairTripCW): the workgroup's LDS scratch, 2 KiB per wave
 };
 template <typename T, int MC, int W>
 struct UpdScanRegs {  // the register images of one row group
@@ -161,7 +162,9 @@ struct UpdScanTripCW1 : UpdScanRegs<T, MC, 1>, CwOneRow {
       raw_issue<B, NTL>(this->rb[j], live ? c.ws + off : c.zero);
     }
   }
+  static constexpr bool DENSE = false;
   __device__ __forceinline__ void land() {}
+  __device__ __forceinline__ void land_cw(const UpdScanCtx<T> &) {}
   // Into registers of their own, merged afterwards: a load INTO ra / rb inside this (rare) branch would make every
   // later use of them wait for whatever is in flight -- with two trips in flight, the next trip's loads.
   __device__ __forceinline__ void reload_cols(const UpdScanCtx<T> &c, const bool (&miss)[1]) {
@@ -226,7 +229,7 @@ struct UpdScanTripCW2 : UpdScanRegs<T, MC, 2>, CwPairRows {
     cols_row<false>(c, 0, t.tb + (lf[0] ? sl[0] : 0));  // (plain loads: see SubsmTripCW2)
     cols_row<false>(c, 1, t.tb + (lf[1] ? sl[1] : 0));
   }
-  __device__ __forceinline__ void land() {
+  __device__ __forceinline__ void land_cw(const UpdScanCtx<T> &) {
     raw_join_bytes(this->rnb, nb_[0], nb_[1]);
     raw_join_bytes(this->riw, iw_[0], iw_[1]);
   }
@@ -329,11 +332,24 @@ struct UpdScanPairTrip : NaturalRows<W> {
 // update), and the pass is bound by its loads again instead of by what it issues.
 // TIGHT: the caller guarantees nold == MC - 1 (every iteration once the memory is full): the one dead unroll slot
 // is the odd lane's last, known at compile time -- no select in front of the other loads.
-template <typename T, int MC, bool NT, bool TIGHT>
+// DN (option "cw_dense"): the layout-free entries of a HALF tile are one contiguous run of each column, [0, c0) or
+// [c0, tf) of the tile's slots: at most 64 entries.  Instead of two 8-byte loads per column, in which every lane
+// takes part (a lane whose row has no bit re-reads the tile's first entry), each lane fetches 16 bytes of the run of
+// ITS column -- lane q of either half of the wave the slots es + 2q, es + 2q + 1, es = the run's start rounded down
+// to an even slot; the lanes behind the run's end are off -- and the entries reach the lanes that sum them through
+// LDS after the wait: one 16-byte write per lane, then an 8-byte read at the slot of each of the pair's two rows.
+// Half the load instructions for the same bytes; what a row without a bit gets only ever meets exact zeros, as the
+// tile's first entry does today (see UpdScanTripCW1) -- such a row that does need its entries fetches them in
+// the kernel body as before (reload_cols).  A run of 64 entries that starts at an odd slot does not fit the 32
+// pieces: that trip loads as before (dense_).
+template <typename T, int MC, bool NT, bool TIGHT, bool DN = false>
 struct UpdScanPairTripCW : CwOneRow {
   static_assert(sizeof(T) == 8, "compact W: fp64");
   static constexpr int H = MC / 2;
   static constexpr int NL = 8 + 4 * H;
+  static constexpr bool DENSE = DN;
+  bool dense_ = false;  // (wave-uniform) this trip's columns wait in the 16-byte images of the run
+  int es_ = 0, re_ = 0;   // the run as loaded: in-tile slots [es_, re_)
   RawOf<T, 1> rx, rl, ru, rg, rr, rd;
   RawOf<T, 2> ra[H], rb[H];
   RawOf<nb_t, 1> rnb;
@@ -358,7 +374,7 @@ struct UpdScanPairTripCW : CwOneRow {
       raw_issue_half<NTL>(qb[jj], 1, (const T *)((gptr)p[jj].y + (dead ? 0 : a1)));
     }
   }
-  __device__ __forceinline__ void issue_cw(const UpdScanCtx<T> &c, int64_t i, int64_t slot, bool lf, int64_t first) {
+  __device__ __forceinline__ void issue_rows(const UpdScanCtx<T> &c, int64_t i, int64_t slot, bool lf) {
     constexpr int B = (int)sizeof(T);
     this->ri_ = i, this->ws_ = slot, this->lf_ = lf;
     raw_issue<B, NT>(rx, c.x + i);
@@ -369,6 +385,44 @@ struct UpdScanPairTripCW : CwOneRow {
     raw_issue<B, NT>(rd, c.d + i);
     raw_issue<1, false>(rnb, (c.ub & 4) ? c.nbd : c.nbd + i);
     raw_issue<1, false>(riw, c.iwhere + i);
+  }
+  __device__ __forceinline__ bool dead_col(const UpdScanCtx<T> &c, int jj) const {  // (that table entry is the zero buffer)
+    const bool hi = threadIdx.x & 32;
+    return TIGHT ? (jj == H - 1 && hi) : (hi && H + jj >= c.nold);
+  }
+  // a full half whose run is the in-tile slots [rs, re) (wave-uniform)
+  __device__ __forceinline__ void issue_cw_run(const UpdScanCtx<T> &c, int64_t i, int64_t slot, bool lf, int64_t first,
+                                               int rs, int re) {
+    const int es = rs & ~1;
+    if (re - es > 64) {  // (the 33rd piece: 64 free rows behind an odd start)
+      issue_cw(c, i, slot, lf, first);
+      return;
+    }
+    issue_rows(c, i, slot, lf);
+    dense_ = true, es_ = es, re_ = re;
+    const bool hi = threadIdx.x & 32;
+    const int q = (int)(threadIdx.x & 31);
+    int tb = hi ? 2 * H : 0;
+    asm volatile("" : "+v"(tb));
+    u64x2 p[H];
+#pragma unroll
+    for (int jj = 0; jj < H; ++jj) p[jj] = *reinterpret_cast<const u64x2 *>(c.ptab + tb + 2 * jj);
+    const bool act = es + 2 * q < re;
+    const int64_t a = first + es + 2 * q;
+    // (a dead unroll slot reads 16 bytes of the zero buffer in every lane: its 32 pieces are all zero)
+#pragma unroll
+    for (int jj = 0; jj < H; ++jj) {
+      const bool dead = dead_col(c, jj);
+      // (ordinary loads inside a divergent branch: the compiler tracks them across the join, see SubsmTripCW2)
+      if (act || dead) {
+        raw_issue<16, false>(ra[jj], (const T *)((gptr)p[jj].x + (dead ? 0 : a)));
+        raw_issue<16, false>(rb[jj], (const T *)((gptr)p[jj].y + (dead ? 0 : a)));
+      }
+    }
+  }
+  __device__ __forceinline__ void issue_cw(const UpdScanCtx<T> &c, int64_t i, int64_t slot, bool lf, int64_t first) {
+    issue_rows(c, i, slot, lf);
+    dense_ = false;
     // (a row whose layout bit is clear reads the first entry of its tile: see UpdScanTripCW1)
     int64_t a0, a1;  // the slots of the pair's rows: the lane below 32, the lane above
     half_pair(lf ? slot : first, a0, a1);
@@ -378,6 +432,33 @@ struct UpdScanPairTripCW : CwOneRow {
     cols<false>(c, a0, a1, ra, rb);
   }
   __device__ __forceinline__ void land() {}
+  __device__ __forceinline__ void land_cw(const UpdScanCtx<T> &c) {
+    if constexpr (DN) {
+      if (dense_) {
+        const bool hi = threadIdx.x & 32;
+        const int q = (int)(threadIdx.x & 31);
+        const bool act = es_ + 2 * q < re_;
+        // where the pair's rows sit in the run as loaded.  A row without a bit reads the run's first piece: an entry
+        // of its tile or, behind an empty run, whatever an earlier column left there (the scratch starts as zeros) --
+        // any finite factor will do, see UpdScanTripCW1
+        const int own = this->lf_ ? (int)(this->ws_ & 127) - es_ : 0;
+        int r0, r1;
+        half_pair(own, r0, r1);
+        // this wave's scratch: [Wy | Ws][lanes below 32 | above][32 pieces].  LDS operations of one wave complete
+        // in the order they were issued (wave_lds_order)
+        i32x4_t *wa = c.scr + (threadIdx.x >> 6) * 128 + (hi ? 32 : 0), *wb = wa + 64;
+        const i32x2_t *pa = reinterpret_cast<const i32x2_t *>(wa), *pb = reinterpret_cast<const i32x2_t *>(wb);
+#pragma unroll
+        for (int jj = 0; jj < H; ++jj) {
+          if (act || dead_col(c, jj)) wa[q] = ra[jj].v, wb[q] = rb[jj].v;
+          wave_lds_order();
+          ra[jj].v.xy = pa[r0], ra[jj].v.zw = pa[r1];
+          rb[jj].v.xy = pb[r0], rb[jj].v.zw = pb[r1];
+          wave_lds_order();
+        }
+      }
+    }
+  }
   // miss[0]: THIS lane's row needs its own entries.  Both lanes of a pair fetch their columns of that row (into
   // registers of their own, merged afterwards: see UpdScanTripCW1).
   __device__ __forceinline__ void reload_cols(const UpdScanCtx<T> &c, const bool (&miss)[1]) {
@@ -411,14 +492,15 @@ struct UpdScanPairTripCW : CwOneRow {
 // The caller passes a row count that is a multiple of 2 V (pairs are always complete) and runs the
 // plain instantiation on the few rows that remain.
 // CW: W in the tile-local free-row layout `lmask` (fp64, MC <= 10; for_tiles_cw)
-template <typename T, int MC, bool NT, bool PIPE, bool NEWROW, bool PAIR = false, bool CW = false, bool TIGHT = false>
-__global__ __launch_bounds__(BLOCK) void update_scan_kernel(
+// DN: UpdScanPairTripCW's dense loads (CW && PAIR)
+template <typename T, int MC, bool NT, bool PIPE, bool NEWROW, bool PAIR, bool CW, bool TIGHT, bool DN>
+__device__ __forceinline__ void update_scan_body(
     int64_t n, const T *__restrict__ x, const T *__restrict__ l, const T *__restrict__ u,
     const nb_t *__restrict__ nbd, const T *__restrict__ g, const T *__restrict__ r,
     const T *__restrict__ d, int dimpl, double stp, iw_t *iwhere, T *tbrk, T *ws, T *wy,
     const T *__restrict__ zero, int64_t ldw, int m, int head, int nold, int itail, int store_pair,
     int store_iw, double cand_hi, uint64_t *ckeys, uint32_t *cidx, uint32_t ccap, uint32_t *ccount,
-    int ub, double *part, const uint64_t *__restrict__ lmask = nullptr) {
+    int ub, double *part, const uint64_t *__restrict__ lmask) {
   static_assert(!CW || (sizeof(T) == 8 && MC <= 10 && !PIPE), "compact W: fp64, MC <= 10, one trip in flight");
   static constexpr UpdScanSlots S{MC, NEWROW};
   constexpr int NA = S.size(), NSUM = S.nsum();
@@ -447,7 +529,13 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
     }
     __syncthreads();
   }
-  const UpdScanCtx<T> ctx{x, l, u, g, r, d, ws, wy, zero, nbd, iwhere, ldw, m, head, nold, ub, ptab};
+  static_assert(!DN || (CW && PAIR), "dense loads: the layout's lane-pair instantiation");
+  __shared__ i32x4_t cw_scr[DN ? (BLOCK / 64) * 128 : 1];
+  if constexpr (DN) {  // (every wave its own 2 KiB: no barrier)
+    i32x4_t *own = cw_scr + (threadIdx.x >> 6) * 128 + (threadIdx.x & 63);
+    own[0] = i32x4_t{0, 0, 0, 0}, own[64] = i32x4_t{0, 0, 0, 0};
+  }
+  const UpdScanCtx<T> ctx{x, l, u, g, r, d, ws, wy, zero, nbd, iwhere, ldw, m, head, nold, ub, ptab, cw_scr};
   __shared__ T dict[16];
   dict_fill<T>(dict, l, u, ub);
   using TripV = std::conditional_t<PAIR, UpdScanPairTrip<T, MC, V, NT>, UpdScanTrip<T, MC, V, NT>>;
@@ -658,7 +746,7 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
     if constexpr (!PAIR) row_stores();
   };
   if constexpr (CW && PAIR)  // (the caller passes whole tiles)
-    for_halves_cw<UpdScanPairTripCW<T, MC, NT, TIGHT>>(n, ctx, lmask, body);
+    for_halves_cw<UpdScanPairTripCW<T, MC, NT, TIGHT, DN>>(n, ctx, lmask, body);
   else if constexpr (CW && NEWROW)  // (one row per lane and trip, two trips in flight: see for_halves_cw)
     for_halves_cw<UpdScanTripCW1<T, MC, NT>>(n, ctx, lmask, body);
   else if constexpr (CW)
@@ -685,6 +773,31 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel(
     }
   }
   block_reduce_store<NA>(acc, NSUM, 1, 1, part, MAX_BLOCKS);
+}
+template <typename T, int MC, bool NT, bool PIPE, bool NEWROW, bool PAIR = false, bool CW = false, bool TIGHT = false>
+__global__ __launch_bounds__(BLOCK) void update_scan_kernel(
+    int64_t n, const T *__restrict__ x, const T *__restrict__ l, const T *__restrict__ u,
+    const nb_t *__restrict__ nbd, const T *__restrict__ g, const T *__restrict__ r,
+    const T *__restrict__ d, int dimpl, double stp, iw_t *iwhere, T *tbrk, T *ws, T *wy,
+    const T *__restrict__ zero, int64_t ldw, int m, int head, int nold, int itail, int store_pair,
+    int store_iw, double cand_hi, uint64_t *ckeys, uint32_t *cidx, uint32_t ccap, uint32_t *ccount,
+    int ub, double *part, const uint64_t *__restrict__ lmask = nullptr) {
+  update_scan_body<T, MC, NT, PIPE, NEWROW, PAIR, CW, TIGHT, false>(
+      n, x, l, u, nbd, g, r, d, dimpl, stp, iwhere, tbrk, ws, wy, zero, ldw, m, head, nold, itail, store_pair, store_iw,
+      cand_hi, ckeys, cidx, ccap, ccount, ub, part, lmask);
+}
+// ... the layout's lane-pair instantiation with UpdScanPairTripCW's dense loads (option "cw_dense")
+template <typename T, int MC, bool NT, bool TIGHT>
+__global__ __launch_bounds__(BLOCK) void update_scan_kernel_dense(
+    int64_t n, const T *__restrict__ x, const T *__restrict__ l, const T *__restrict__ u,
+    const nb_t *__restrict__ nbd, const T *__restrict__ g, const T *__restrict__ r,
+    const T *__restrict__ d, int dimpl, double stp, iw_t *iwhere, T *tbrk, T *ws, T *wy,
+    const T *__restrict__ zero, int64_t ldw, int m, int head, int nold, int itail, int store_pair,
+    int store_iw, double cand_hi, uint64_t *ckeys, uint32_t *cidx, uint32_t ccap, uint32_t *ccount,
+    int ub, double *part, const uint64_t *__restrict__ lmask) {
+  update_scan_body<T, MC, NT, false, true, true, true, TIGHT, true>(
+      n, x, l, u, nbd, g, r, d, dimpl, stp, iwhere, tbrk, ws, wy, zero, ldw, m, head, nold, itail, store_pair, store_iw,
+      cand_hi, ckeys, cidx, ccap, ccount, ub, part, lmask);
 }
 // ---- more than 20 old pairs with formk's new-row sums: the split pass ----
 // Eight sums per column pair are 256 fp64 accumulators at MC = 32 -- no sharing between two lanes brings that
@@ -781,21 +894,24 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
           // the whole tiles; the rows behind them (< one tile) go to the plain instantiation as one more workgroup,
           // whose partials land in column `gr` of the partial-sum matrix -- as the natural-order MC = 20 pass does
           const int64_t n_main = n / CW_TILE * CW_TILE, n_rest = n - n_main;
-#define LB_PAIR_CW(NTV, TIGHTV)                                                                                   \
+#define LB_PAIR_CW_(...)                                                                                           \
   {                                                                                                               \
-    gr = grid_for_w(q, n_main, VecOf<T>::V,                                                                       \
-                    (const void *)&update_scan_kernel<T, 10, NTV, false, true, true, true, TIGHTV>);              \
-    hipLaunchKernelGGL((update_scan_kernel<T, 10, NTV, false, true, true, true, TIGHTV>), dim3(gr), dim3(BLOCK), 0, \
+    gr = grid_for_w(q, n_main, VecOf<T>::V, (const void *)&__VA_ARGS__);                                                 \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3(gr), dim3(BLOCK), 0,                                                          \
                        q.stream, n_main, x, l, u, nbd, g, r, d, dimpl, stp, iwhere, tbrk, w.ws, w.wy, w.zero,       \
                        w.ld, w.m, head, nold, itail, store_pair, store_iw, cand_hi, ckeys, cidx, ccap, ccount, ub,   \
                        q.part(), w.lmask);                                                                          \
   }
+#define LB_PAIR_CW(NTV, TIGHTV)                                                      \
+  { if (q.cw_dense) { q.n_dense_update++; LB_PAIR_CW_(update_scan_kernel_dense<T, 10, NTV, TIGHTV>) } \
+    else LB_PAIR_CW_(update_scan_kernel<T, 10, NTV, false, true, true, true, TIGHTV>) }
           if (nold == 9) {
             if (q.nt) LB_PAIR_CW(true, true) else LB_PAIR_CW(false, true)
           } else {
             if (q.nt) LB_PAIR_CW(true, false) else LB_PAIR_CW(false, false)
           }
 #undef LB_PAIR_CW
+#undef LB_PAIR_CW_
           nblocks = gr;
           if (n_rest > 0) {
             LB_LAUNCHED(q);

@@ -65,6 +65,8 @@ struct Queue {
   // layout the context can have + the deferred line-search sums, whatever the current number of pairs)
   int split_base_min = 0;
   bool nt = false;  // nontemporal loads in the W-pass kernels (W much larger than the Infinity Cache)
+  bool cw_dense = true;  // option "cw_dense": the layout's passes fetch a tile's run of a column by 16-byte loads
+  int64_t n_dense_subsm = 0, n_dense_update = 0;  // launches of the two dense kernels (lbfgsb_hip_dense_launches)
   Tune tune{};
   // first kernel launch that failed since the last check (hipGetLastError right behind the launch,
   // so that the error is reported with the kernel's name and not at the next stream sync)

@@ -303,6 +303,9 @@
     closed_form = nclosed, three_pass = nthreepass;
   }
   int64_t freev_skipped() const override { return nfreev_skipped; }
+  void dense_launches(int64_t &storing, int64_t &update) const override {
+    storing = q.n_dense_subsm, update = q.n_dense_update;
+  }
   void compact_stats(int64_t &packs, int64_t &unpacks, int &packed, int &eligible) const override {
     packs = ncw_pack, unpacks = ncw_unpack, packed = cw_packed ? 1 : 0, eligible = cw_eligible() ? 1 : 0;
   }

@@ -757,6 +757,12 @@ class DeviceSolver:
         check(self.lib.lbfgsb_hip_comm_info(self.h, C.byref(a), C.byref(b), C.byref(k)))
         return int(a.value), int(b.value), int(k.value)
 
+    def dense_launches(self):
+        """option cw_dense: launches of the (storing pass's, update pass's) dense kernel -- lbfgsb_hip_dense_launches"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(self.lib.lbfgsb_hip_dense_launches(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def compact_stats(self):
         """option compact_w: (packs, unpacks, packed now, eligible) -- lbfgsb_hip_compact_stats"""
         a, b = C.c_int64(0), C.c_int64(0)
