@@ -481,6 +481,39 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  * When, streams, the collective rule and the refusals are qn_apply's (every rank calls with its own rows).
  * LBFGSB_E_ARG in addition, changing nothing: NULL h_r / h_bulk / out, cap < 0, cap > 0 with h_lambda = NULL, k < 1,
  * k > 128, an index outside 0 .. r-1, ldo < n_local, a mode other than B / H.
+ *
+ * The model plus a diagonal.  A Laplace posterior with a Gaussian prior has the precision B + diag(tau); a
+ * trust-region, Levenberg-Marquardt or proximal Newton step solves with B + mu I; the model on the free variables is
+ * the limit d_i -> infinity on the rows at bounds.  None of them is a function of B's spectrum.  With
+ * Delta = (theta + mu) I + D, w = 1 / Delta elementwise (w_i = 0 on a pinned row) and W = [Y, theta S]:
+ *   (B + mu I + D)^-1 = diag(w) + diag(w) W K^-1 W' diag(w),   K = M^-1 - W' diag(w) W   (2col x 2col),
+ *   log det           = sum over the free rows of log Delta_i + log |det K| - log |det M^-1|,
+ *   diag              = w_i + w_i^2 r_i' K^-1 r_i,   r_i = row i of W,
+ * with M^-1 = [[-D_sy, L'], [L, theta S'S]] from Sy and Ss.  K is factorised on the host by two Cholesky factors (the
+ * negated (1, 1) block, then the Schur complement); it has col negative and col positive eigenvalues exactly when the
+ * shifted model is positive definite on the free rows.
+ *   qn_shift_set: d (n_local reals of the context's kind on the device, or NULL for D = 0) is read once on the
+ *     context's stream and need not outlive the call; the weights go to a buffer of the context (n_local doubles).
+ *     d_i = +inf pins row i: w_i = 0 exactly, its row of every later solve / diag output is +0 and it is left out of
+ *     log det; *h_pinned (may be NULL) receives the number of pinned rows over all ranks.  All rows pinned is legal:
+ *     solves return 0 and log det is 0.  One pass over d (16 B per row in fp64) and ceil(2col / 4) weighted passes
+ *     over W, then the factor.  LBFGSB_E_ARG, the context as it was (an earlier shift of the same pairs stays in
+ *     force): a NaN or infinite mu, any row with theta + mu + d_i <= 0 or NaN (counted by the pass over d), more than
+ *     LBFGSB_QN_ROOT_MAXCOL stored pairs.  LBFGSB_E_STATE, the context as it was: K does not have the inertia
+ *     (col, col) -- the shifted model is not positive definite on the free rows.
+ *   qn_shift_solve: out_j = (B + mu I + D)^-1 v_j on the free rows (+0 on the pinned ones, whatever v holds there),
+ *     j < k, vector j at v + j*ldv, result j at out + j*ldo; out may not overlap v.  Any k: per block of 4 vectors one
+ *     weighted W'v pass and one weighted expansion, each 8 B per row more than qn_apply's.
+ *   qn_shift_logdet: *h_logdet = log det of the shifted model on the free rows, a host double with the same bits on
+ *     every rank; no device pass (the sum over log Delta_i is reduced inside qn_shift_set).  No stored pair: the sum
+ *     over the free rows of log(theta + mu + d_i).
+ *   qn_shift_diag: out = the diagonal of the inverse above (n_local reals), at most 32 stored pairs as qn_diag.
+ * The factor belongs to the pairs it was made of: after a return that changes the pairs or theta (and before any
+ * qn_shift_set) solve, logdet and diag return LBFGSB_E_STATE ("call qn_shift_set again"); they never use old weights
+ * with new pairs.  When, streams, the collective rule, REAL32 (d, v, out fp32; the weights and every sum fp64) and
+ * the refusals are qn_apply's, and the run does not notice the calls.
+ * Not offered: the product (B + mu I + D) v -- it is qn_apply(LBFGSB_QN_B) plus an axpy with mu + d --, and roots or
+ * draws of the shifted model.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
@@ -506,6 +539,10 @@ int lbfgsb_hip_qn_gram(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const void *v, 
 #define LBFGSB_QN_EIG_CUT 1e-8
 int lbfgsb_hip_qn_eig(lbfgsb_hip_ctx *ctx, int mode, int32_t cap, int32_t *h_r, double *h_bulk, double *h_lambda);
 int lbfgsb_hip_qn_eigvec(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int32_t *h_which, void *out, int64_t ldo);
+int lbfgsb_hip_qn_shift_set(lbfgsb_hip_ctx *ctx, const void *d, double mu, int64_t *h_pinned);
+int lbfgsb_hip_qn_shift_solve(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo);
+int lbfgsb_hip_qn_shift_logdet(lbfgsb_hip_ctx *ctx, double *h_logdet);
+int lbfgsb_hip_qn_shift_diag(lbfgsb_hip_ctx *ctx, void *out);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.

@@ -7,9 +7,9 @@ anywhere, but every call that computes raises `LbfgsbError` when the library or
 a gfx950 device is missing.
 """
 from .capi import LbfgsbError, lib_path, load_library, build_library  # noqa: F401
-from .solver import DeviceSolver, QnOperator, KktReport, setulb, wa_length, TASK_LEN  # noqa: F401
+from .solver import DeviceSolver, QnOperator, QnShifted, KktReport, setulb, wa_length, TASK_LEN  # noqa: F401
 from .capi import QN_B, QN_H, QN_B_SQRT, QN_H_SQRT  # noqa: F401
 from .distributed import block_partition, attach_rccl, attach_host_group  # noqa: F401
 
-__all__ = ["LbfgsbError", "DeviceSolver", "QnOperator", "KktReport", "QN_B", "QN_H", "QN_B_SQRT", "QN_H_SQRT",
+__all__ = ["LbfgsbError", "DeviceSolver", "QnOperator", "QnShifted", "KktReport", "QN_B", "QN_H", "QN_B_SQRT", "QN_H_SQRT",
            "setulb", "wa_length", "load_library", "build_library", "lib_path", "TASK_LEN"]

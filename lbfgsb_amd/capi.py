@@ -66,6 +66,10 @@ PROTOTYPES = {
     "lbfgsb_hip_qn_eig": (C.c_int, [_vp, C.c_int, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double)]),
     "lbfgsb_hip_qn_eigvec": (C.c_int, [_vp, C.c_int, C.c_int64, C.POINTER(C.c_int32), _vp, C.c_int64]),
+    "lbfgsb_hip_qn_shift_set": (C.c_int, [_vp, _vp, C.c_double, C.POINTER(C.c_int64)]),
+    "lbfgsb_hip_qn_shift_solve": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
+    "lbfgsb_hip_qn_shift_logdet": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "lbfgsb_hip_qn_shift_diag": (C.c_int, [_vp, _vp]),
     "lbfgsb_hip_kkt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "lbfgsb_hip_kkt_list": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp]),
     "lbfgsb_hip_import_state": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -300,6 +300,24 @@ int lbfgsb_hip_qn_eigvec(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int32_t
   if (k < 1 || k > 128 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_eigvec: k < 1, k > 128 or ldo < n_local");
   return ctx->qn_eigvec(mode, k, h_which, out, ldo);
 }
+int lbfgsb_hip_qn_shift_set(lbfgsb_hip_ctx *ctx, const void *d, double mu, int64_t *h_pinned) {
+  if (!ctx) return fail(LBFGSB_E_ARG, "qn_shift_set: NULL argument");
+  if (!std::isfinite(mu)) return fail(LBFGSB_E_ARG, "qn_shift_set: mu is not finite");
+  return ctx->qn_shift_set(d, mu, h_pinned);
+}
+int lbfgsb_hip_qn_shift_solve(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) {
+  if (!ctx || !v || !out) return fail(LBFGSB_E_ARG, "qn_shift_solve: NULL argument");
+  if (k < 1 || ldv < ctx->n || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_shift_solve: k < 1 or ld < n_local");
+  return ctx->qn_shift_solve(k, v, ldv, out, ldo);
+}
+int lbfgsb_hip_qn_shift_logdet(lbfgsb_hip_ctx *ctx, double *h_logdet) {
+  if (!ctx || !h_logdet) return fail(LBFGSB_E_ARG, "qn_shift_logdet: NULL argument");
+  return ctx->qn_shift_logdet(h_logdet);
+}
+int lbfgsb_hip_qn_shift_diag(lbfgsb_hip_ctx *ctx, void *out) {
+  if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_shift_diag: NULL argument");
+  return ctx->qn_shift_diag(out);
+}
 
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
                    const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,

@@ -249,6 +249,72 @@ inline int qn_gram_combine(int col, int k, double alpha, const double *p, const 
   return 0;
 }
 
+// ---- the model plus a diagonal (lbfgsb_hip_qn_shift_*, solver_qn.inl) ----
+// With Delta = (theta + mu) I + D, w = 1 / Delta (0 on a pinned row), W = [Y, theta S] and bmv's middle matrix M,
+//   (B + mu I + D)^-1 = diag(w) + diag(w) W K^-1 W' diag(w),   K = M^-1 - W' diag(w) W,
+//   M^-1 = [[-D_sy, L'], [L, theta S'S]]  (D_sy, L: the diagonal and the strict lower triangle of S'Y),
+// so K = [[-A, Bm'], [Bm, C]] with A = D_sy + Y'wY, Bm = L - theta S'wY, C = theta S'S - theta^2 S'wS.  When the shifted
+// model is positive definite on the free rows K has col negative and col positive eigenvalues, and formk's route
+// factorises it: A = R1'R1, X = R1^-T Bm', C + X'X = R2'R2 (the Schur complement).
+//
+// sy: S'Y, lower triangle and diagonal read (sy[i + j ldsy], i >= j); sts: S'S, all of it (sts[i + j ldss]); gw: the
+// weighted Gram [S, Y]' diag(w) [S, Y], symmetric, 2col x 2col with the S block first -- NULL stands for zero, K = M^-1.
+// kf (2col x 2col, column-major) receives R1 in the upper triangle of its (1, 1) block, X in the (1, 2) block and R2
+// in the upper triangle of the (2, 2) block; *logdet = log |det K|.  Returns 0, 1 when A is not positive definite (a
+// stored pair with s'y <= 0) or 2 when the Schur complement is not: K does not have the inertia (col, col).
+inline int qn_shift_factor(int col, double theta, const double *sy, int ldsy, const double *sts, int ldss,
+                           const double *gw, double *kf, double *logdet) {
+  const int d = 2 * col;
+  *logdet = 0.0;
+  if (col == 0) return 0;
+  std::fill(kf, kf + (size_t)d * d, 0.0);
+  Mat k{kf, d}, r1{kf, d}, r2{kf + col + (size_t)col * d, d};
+  auto g = [&](int i, int j) { return gw ? gw[i + (size_t)j * d] : 0.0; };
+  for (int j = 0; j < col; ++j)
+    for (int i = 0; i <= j; ++i) k(i, j) = (i == j ? sy[i + (size_t)i * ldsy] : 0.0) + g(col + i, col + j);
+  if (dpofa(r1, col)) return 1;
+  for (int j = 0; j < col; ++j) {  // column j of X: R1' x = row j of Bm
+    double *x = &k(0, col + j);
+    for (int i = 0; i < col; ++i) x[i] = (j > i ? sy[j + (size_t)i * ldsy] : 0.0) - theta * g(j, col + i);
+    dtrsl(r1, col, x, 11);
+  }
+  for (int j = 0; j < col; ++j)
+    for (int i = 0; i <= j; ++i)
+      k(col + i, col + j) = (theta * sts[i + (size_t)j * ldss] - theta * theta * g(i, j)) +
+                            dot_seq(col, &k(0, col + i), &k(0, col + j));
+  if (dpofa(r2, col)) return 2;
+  double s = 0.0;
+  for (int i = 0; i < d; ++i) s = s + std::log(k(i, i));
+  *logdet = 2.0 * s;
+  return 0;
+}
+
+// (cs; cy) of out = w o (v + S cs + Y cy) from stv = S'(w o v), ytv = Y'(w o v) and qn_shift_factor's kf:
+// K (z1; z2) = (ytv; theta stv), cy = z1, cs = theta z2
+inline int qn_shift_coef(int col, double theta, const double *kf, const double *stv, const double *ytv, double *cs,
+                         double *cy) {
+  if (col == 0) return 0;
+  const int d = 2 * col;
+  double *p = const_cast<double *>(kf);
+  Mat k{p, d}, r1{p, d}, r2{p + col + (size_t)col * d, d};
+  double t[1024], z[1024];
+  for (int i = 0; i < col; ++i) t[i] = ytv[i];
+  int info = dtrsl(r1, col, t, 11);  // t = R1^-T b1
+  if (info) return info;
+  for (int j = 0; j < col; ++j) z[j] = theta * stv[j] + dot_seq(col, &k(0, col + j), t);  // b2 + X't
+  info = dtrsl(r2, col, z, 11);
+  if (info) return info;
+  dtrsl(r2, col, z, 1);  // z2
+  for (int i = 0; i < col; ++i) {  // X z2 - t
+    double s = -t[i];
+    for (int j = 0; j < col; ++j) s = s + k(i, col + j) * z[j];
+    cy[i] = s;
+  }
+  dtrsl(r1, col, cy, 1);  // z1
+  for (int i = 0; i < col; ++i) cs[i] = theta * z[i];
+  return 0;
+}
+
 // ---- the square root and the log-determinant of the model (lbfgsb_hip_qn_apply's root modes, qn_logdet, qn_draw) ----
 // Both models are A = alpha I + W N W' with W = [S, Y] and G = W'W.  With P = G^(1/2) and P N P = V diag(delta) V'
 // (delta: the non-zero eigenvalues of W N W'),

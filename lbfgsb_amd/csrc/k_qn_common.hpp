@@ -1,6 +1,6 @@
-// k_qn_common.hpp -- what the kernel files of the curvature-model operator share (k_qn.hip, k_qn_draw.hip): the slot
-// of a row in the layout W is in, and the dispatch of a launch over the column capacity MC of a tile, the block of
-// K vectors, the layout (CW), the rows per lane (V) and the cache policy of the loads (NT).
+// k_qn_common.hpp -- what the kernel files of the curvature-model operator share (k_qn.hip, k_qn_draw.hip,
+// k_qn_shift.hip): the slot of a row in the layout W is in, and the dispatch of a launch over the column capacity MC
+// of a tile, the block of K vectors, the layout (CW), the rows per lane (V) and the cache policy of the loads (NT).
 #pragma once
 #include "kernels_common.hpp"
 

@@ -565,6 +565,28 @@ template <typename T>
 hipError_t launch_qn_diag(const Queue &q, int64_t n, WStore<T> w, int head, int col, const double *np, double alpha,
                           T *out);
 
+// The model plus a diagonal (k_qn_shift.hip, lbfgsb_hip_qn_shift_*): the row-weighted twins of the passes above.  The
+// weights wgt (n doubles in both real kinds, natural row order) are w_i = 1 / (shift + d_i), 0 on a pinned row.
+// wgt[i] = 1 / (shift + d[i]) (d may be NULL: all zero; d[i] = +inf pins the row: 0); res[0] = the sum of
+// log(shift + d[i]) over the free rows, res[1] = the pinned rows, res[2] = the rows with shift + d[i] <= 0 or NaN
+constexpr int QN_SHIFT_SUMS = 3;
+template <typename T>
+hipError_t launch_qn_shift_w(const Queue &q, int64_t n, const T *d, double shift, double *wgt, double *part,
+                             double *res);
+// launch_qn_wtv's plain pass on wgt o v_k (vslot: the vectors are columns of W, the weights still natural)
+template <typename T>
+hipError_t launch_qn_shift_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                               QnVecs<T> v, bool vslot, const double *wgt, double *part, double *res);
+// first: out_k = wgt o (src_k + [S, Y](:, tile) coef[k * 2 mc ...]); else out_k = src_k + wgt o ([S, Y] coef) (src_k
+// is out_k: the second and later tiles).  Rows with wgt = 0 of a first tile are +0 whatever src holds there
+template <typename T>
+hipError_t launch_qn_shift_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                                  const double *coef, QnVecs<T> src, const double *wgt, bool first, QnOuts<T> out);
+// out_i = wgt_i + wgt_i^2 r_i' N r_i (col <= 32; np as launch_qn_diag takes it)
+template <typename T>
+hipError_t launch_qn_shift_diag(const Queue &q, int64_t n, WStore<T> w, int head, int col, const double *np,
+                                const double *wgt, T *out);
+
 // The basis pass (k_qn_eig.hip): out_j (+)= [S, Y](:, tile) coef[j * 2 mc ...] for ALL j < k <= QN_BASIS_KMAX in one
 // launch, output j at out + j * ldo; the tile's columns are read once per row.  acc: add to what out holds (the tiles
 // after the first).  coef: DEVICE memory, 2 mc k doubles as qn_basis_pack lays them out, read through uniform (scalar)

@@ -169,6 +169,11 @@ struct lbfgsb_hip_ctx {
                        int64_t ldg) = 0;
   virtual int qn_eig(int mode, int32_t cap, int32_t *h_r, double *h_bulk, double *h_lambda) = 0;
   virtual int qn_eigvec(int mode, int64_t k, const int32_t *h_which, void *out, int64_t ldo) = 0;
+  // the model plus a diagonal (lbfgsb_hip_qn_shift_*)
+  virtual int qn_shift_set(const void *d, double mu, int64_t *h_pinned) = 0;
+  virtual int qn_shift_solve(int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) = 0;
+  virtual int qn_shift_logdet(double *h_logdet) = 0;
+  virtual int qn_shift_diag(void *out) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

@@ -3,7 +3,8 @@
 // lbfgsb_hip_qn_diag; k_qn.hip has the kernels, host_dense.hpp the 2col x 2col algebra), their
 // symmetric square roots, log-determinants and draws (lbfgsb_hip_qn_logdet, lbfgsb_hip_qn_draw; k_qn_draw.hip), and
 // quadratic forms and Gaussian log-densities (lbfgsb_hip_qn_quad, qn_logpdf, qn_draw_logpdf),
-// and Gram matrices on blocks of vectors (lbfgsb_hip_qn_gram; section 10d).
+// and Gram matrices on blocks of vectors (lbfgsb_hip_qn_gram; section 10d), and solves, log-determinants and diagonals
+// of the model plus a diagonal (lbfgsb_hip_qn_shift_*; k_qn_shift.hip, section 10f).
 // Which launches a pass over W is made of and where their sums land is decided in one place, qn_plan.hpp (host-only,
 // walked on the CPU by tests/qn_plan_check.cpp): every W'V pass here goes through qn_sums_by on a plan, every
 // expansion through qn_expand_by, and a new operator hooks in with a plan and a launch of its own.
@@ -588,6 +589,189 @@
                       "qn_basis"));
     return qn_finish();
   }
+
+  // ---- the model plus a diagonal (lbfgsb_hip_qn_shift_*; k_qn_shift.hip, host_dense.hpp qn_shift_factor / _coef,
+  // DESIGN.md section 10f): (B + mu I + D)^-1 = diag(w) + diag(w) W K^-1 W' diag(w) on the rows that are not pinned.
+  // qn_shift_set makes the weights and the factor of K for the pairs of this generation; solve, logdet and diag use
+  // them while that generation lasts and refuse afterwards.
+  struct QnShift {
+    bool have = false;
+    int64_t gen = -1;            // the pair generation the weights and the factor were made at
+    int64_t pinned = 0;          // rows with d_i = +inf, all ranks
+    double logdet = 0.0;         // log det of the shifted model on the free rows
+    std::vector<double> kf;      // qn_shift_factor's factor of K (2col x 2col)
+    double *d_w[2] = {nullptr, nullptr};  // the weights (n doubles, natural order); a set that is refused leaves the
+    int cur = 0;                          // live ones alone: it writes the other buffer, and success swaps
+    double *d_n = nullptr;       // qn_shift_diag's packed N
+    bool n_ok = false;           // ... is the one of this factor
+  } qsh;
+  int qn_shift_live() {
+    if (!qsh.have || qsh.gen != qn.gen)
+      return fail(LBFGSB_E_STATE, qsh.have ? "qn_shift: the pairs have changed since lbfgsb_hip_qn_shift_set: call "
+                                             "qn_shift_set again"
+                                           : "qn_shift: no shift is set: call qn_shift_set again");
+    return 0;
+  }
+  // M^-1's blocks (col x col each): S'S, all of it, and S'Y, the lower triangle and the diagonal -- from Ss and Sy.  In
+  // a REAL32 context both come from the stored pairs instead (qn_gram_ss, qn_gram): Ss and Sy are summed from the
+  // steps before these are rounded into W, and K = M^-1 - W'wW cancels to the weighted part's size (at mu = 0, D = 0
+  // its (2, 2) block is rounding noise), where an M^-1 that is 1e-7 off the pairs shows in full
+  int qn_shift_minv(std::vector<double> &sts, std::vector<double> &syl) {
+    const int col = qn.col;
+    if (sizeof(T) == 4) {
+      CHK(qn_gram_ss());
+      CHK(qn_gram());
+    }
+    sts.assign((size_t)col * col, 0.0), syl.assign((size_t)col * col, 0.0);
+    for (int j = 0; j < col; ++j)
+      for (int i = 0; i < col; ++i) {
+        sts[i + (size_t)j * col] = sizeof(T) == 4 ? 0.5 * (qn.sts[i + (size_t)j * col] + qn.sts[j + (size_t)i * col])
+                                                  : ss[(size_t)std::min(i, j) + (size_t)std::max(i, j) * m];
+        if (i >= j) syl[i + (size_t)j * col] = sizeof(T) == 4 ? qn.sty[i + (size_t)j * col] : sy[i + (size_t)j * m];
+      }
+    return 0;
+  }
+  // gw = [S, Y]' diag(w) [S, Y] over all rows (2col x 2col, the S block first): the weighted W'V pass with the
+  // columns of W as its vectors, 4 at a time, then symmetrised as qn_model_mats does
+  int qn_shift_gram(const double *wgt, double *gw) {
+    const int col = qn.col, d = 2 * col;
+    const lbk::WStore<T> w = Wc();
+    std::vector<double> sums((size_t)d * lbk::QN_KMAX);
+    for (int k0 = 0; k0 < d; k0 += lbk::QN_KMAX) {
+      const int kc = std::min(lbk::QN_KMAX, d - k0);
+      const T *v[lbk::QN_KMAX];
+      for (int kk = 0; kk < kc; ++kk) {
+        const int j = k0 + kk;
+        v[kk] = (j < col ? ws : wy) + (int64_t)((qn.head - 1 + (j < col ? j : j - col)) % m) * ld;
+      }
+      CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::None), sums.data(), nullptr, [&](const lbk::QnPiece &p) {
+        lbk::QnVecs<T> vv{};
+        for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
+        return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, true, wgt,
+                                                       qn.d_part, qn.d_res + p.off),
+                           "qn_shift_wtv");
+      }));
+      for (int kk = 0; kk < kc; ++kk)
+        std::copy_n(sums.data() + (size_t)kk * d, d, gw + (size_t)(k0 + kk) * d);
+    }
+    for (int j = 0; j < d; ++j)
+      for (int i = 0; i < j; ++i) {
+        const double v = 0.5 * (gw[i + (size_t)j * d] + gw[j + (size_t)i * d]);
+        gw[i + (size_t)j * d] = gw[j + (size_t)i * d] = v;
+      }
+    return 0;
+  }
+  int qn_shift_set(const void *d_, double mu, int64_t *h_pinned) override {
+    CHK(qn_ready());
+    const int col = qn.col, d = 2 * col;
+    if (col > LBFGSB_QN_ROOT_MAXCOL) return fail(LBFGSB_E_ARG, "qn_shift_set: more than 64 stored pairs");
+    if (col > 0 && qn.theta_gram) CHK(qn_gram());  // (theta of an imported state)
+    const double shift = qn.theta + mu;
+    if (!d_ && !(shift > 0.0)) return fail(LBFGSB_E_ARG, "qn_shift_set: theta + mu <= 0");
+    // the first pass: the weights, sum log Delta over the free rows, the pinned and the refused rows
+    const bool live = qsh.have && qsh.gen == qn.gen;
+    const int dst = live ? 1 - qsh.cur : qsh.cur;
+    if (!qsh.d_w[dst]) HIPCHK(own.device(&qsh.d_w[dst], (size_t)std::max<int64_t>(n, 1) * sizeof(double)));
+    double *wgt = qsh.d_w[dst];
+    CHK(qn_launched(lbk::launch_qn_shift_w<T>(q, n, (const T *)d_, shift, wgt, qn.d_part, qn.d_res), "qn_shift_w"));
+    CHK(qn_reduce(lbk::QN_SHIFT_SUMS));
+    const double sumlog = qn.h_res[0], pinned = qn.h_res[1], bad = qn.h_res[2];
+    if (bad > 0.0)
+      return fail(LBFGSB_E_ARG, "qn_shift_set: theta + mu + d_i <= 0 or NaN on " + std::to_string((long long)bad) +
+                                    " rows");
+    std::vector<double> kf((size_t)d * d + 1), km((size_t)d * d + 1);
+    double ldk = 0.0, ldm = 0.0;
+    if (col > 0) {
+      std::vector<double> gw((size_t)d * d), sts, syl;
+      CHK(qn_shift_minv(sts, syl));
+      CHK(qn_shift_gram(wgt, gw.data()));
+      if (lbh::qn_shift_factor(col, qn.theta, syl.data(), col, sts.data(), col, nullptr, km.data(), &ldm))
+        return fail(LBFGSB_E_STATE, "qn_shift_set: the middle matrix is not factorisable (s'y <= 0 or S'S singular)");
+      if (lbh::qn_shift_factor(col, qn.theta, syl.data(), col, sts.data(), col, gw.data(), kf.data(), &ldk))
+        return fail(LBFGSB_E_STATE, "qn_shift_set: the shifted model is not positive definite on the free rows");
+    }
+    qsh.kf.swap(kf);
+    qsh.logdet = sumlog + (ldk - ldm);
+    qsh.pinned = (int64_t)pinned;
+    qsh.cur = dst, qsh.gen = qn.gen, qsh.have = true, qsh.n_ok = false;
+    if (h_pinned) *h_pinned = qsh.pinned;
+    return 0;
+  }
+  int qn_shift_logdet(double *h_logdet) override {
+    CHK(qn_ready());
+    CHK(qn_shift_live());
+    *h_logdet = qsh.logdet;
+    return 0;
+  }
+  // out_j = w o (v_j + S cs_j + Y cy_j): per block of QN_KMAX vectors the weighted W'V pass, the coefficients from
+  // the factor, the weighted expansion
+  int qn_shift_solve(int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) override {
+    CHK(qn_ready());
+    CHK(qn_shift_live());
+    const int col = qn.col;
+    const lbk::WStore<T> w = Wc();
+    const double *wgt = qsh.d_w[qsh.cur];
+    const T *v = (const T *)v_;
+    T *out = (T *)out_;
+    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf(sums.size());
+    for (int64_t k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
+      const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
+      const T *vp[lbk::QN_KMAX];
+      for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (k0 + kk) * ldv;
+      if (col > 0) {
+        CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::None), sums.data(), nullptr, [&](const lbk::QnPiece &p) {
+          lbk::QnVecs<T> vv{};
+          for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = vp[p.k0 + kk];
+          return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, false, wgt,
+                                                         qn.d_part, qn.d_res + p.off),
+                             "qn_shift_wtv");
+        }));
+        for (int kk = 0; kk < kc; ++kk) {
+          const double *sv = sums.data() + (size_t)kk * 2 * col;
+          double *c = cf.data() + (size_t)kk * 2 * col;
+          if (lbh::qn_shift_coef(col, qn.theta, qsh.kf.data(), sv, sv + col, c, c + col))
+            return fail(LBFGSB_E_STATE, "qn_shift_solve: a zero pivot in the factor of K");
+        }
+      }
+      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
+        lbk::QnVecs<T> src{};
+        lbk::QnOuts<T> dst{};
+        for (int kk = 0; kk < p.k; ++kk) {
+          dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
+          src.p[kk] = p.c0 == 0 ? vp[p.k0 + kk] : dst.p[kk];
+        }
+        return qn_launched(lbk::launch_qn_shift_expand<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef, src, wgt,
+                                                          p.c0 == 0, dst),
+                           "qn_shift_expand");
+      }));
+    }
+    return qn_finish();
+  }
+  // out_i = w_i + w_i^2 r_i' N r_i, N = K^-1 in the [S, Y] basis: the matrix of qn_shift_coef's map
+  int qn_shift_diag(void *out_) override {
+    CHK(qn_ready());
+    CHK(qn_shift_live());
+    const int col = qn.col;
+    if (col > lbk::MAXM) return fail(LBFGSB_E_ARG, "qn_shift_diag: more than 32 stored pairs");
+    if (!qsh.d_n) HIPCHK(own.device(&qsh.d_n, (size_t)QN_NP * sizeof(double)));
+    if (!qsh.n_ok) {
+      std::vector<double> nm((size_t)4 * col * col + 1);
+      if (col > 0) {
+        const int info = lbh::qn_nmat(col, [&](const double *stv, const double *ytv, double *cs, double *cy) {
+          return lbh::qn_shift_coef(col, qn.theta, qsh.kf.data(), stv, ytv, cs, cy);
+        }, nm.data());
+        if (info) return fail(LBFGSB_E_STATE, "qn_shift_diag: a zero pivot in the factor of K");
+      }
+      HIPCHK(hipStreamSynchronize(stream));  // (the staging buffer may still feed an earlier copy)
+      lbh::qn_pack_n(col, lbk::maxc_for(std::max(col, 1)), nm.data(), qn.h_n);
+      HIPCHK(hipMemcpyAsync(qsh.d_n, qn.h_n, (size_t)QN_NP * sizeof(double), hipMemcpyHostToDevice, stream));
+      qsh.n_ok = true;
+    }
+    CHK(qn_launched(lbk::launch_qn_shift_diag<T>(q, n, Wc(), qn.head, col, qsh.d_n, qsh.d_w[qsh.cur], (T *)out_),
+                    "qn_shift_diag"));
+    return qn_finish();
+  }
+
   int qn_finish() {
     if (!(flags & LBFGSB_F_NO_RETURN_SYNC)) {
       HIPCHK(hipStreamSynchronize(stream));

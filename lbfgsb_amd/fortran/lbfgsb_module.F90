@@ -50,6 +50,8 @@
       public :: lbfgsb_qn_quad, lbfgsb_qn_logpdf, lbfgsb_qn_draw_logpdf   ! d'A d and Gaussian log-densities
       public :: lbfgsb_qn_gram                          ! the k x k matrix (V - center)' A (V - center)
       public :: lbfgsb_qn_eig, lbfgsb_qn_eigvec         ! eigenvalues and unit eigenvectors of B or H
+      public :: lbfgsb_qn_shift_set, lbfgsb_qn_shift_solve, lbfgsb_qn_shift_logdet, lbfgsb_qn_shift_diag
+                                                       ! solves, log det and diagonal of (B + mu I + diag(d))^-1
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
                                                        ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
       ! slots of lbfgsb_kkt's cnt(:) and val(:): the header's LBFGSB_KKT_* indices + 1 (Fortran arrays start at 1)
@@ -167,6 +169,30 @@
             real(c_double) :: logdet
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_logdet
+         function lbfgsb_hip_qn_shift_set(ctx,d,mu,pinned) bind(C,name='lbfgsb_hip_qn_shift_set') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, d
+            real(c_double),value :: mu
+            integer(c_int64_t) :: pinned
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_set
+         function lbfgsb_hip_qn_shift_solve(ctx,k,v,ldv,out,ldo) bind(C,name='lbfgsb_hip_qn_shift_solve') result(rc)
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, v, out
+            integer(c_int64_t),value :: k, ldv, ldo
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_solve
+         function lbfgsb_hip_qn_shift_logdet(ctx,logdet) bind(C,name='lbfgsb_hip_qn_shift_logdet') result(rc)
+            import :: c_int, c_double, c_ptr
+            type(c_ptr),value :: ctx
+            real(c_double) :: logdet
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_logdet
+         function lbfgsb_hip_qn_shift_diag(ctx,out) bind(C,name='lbfgsb_hip_qn_shift_diag') result(rc)
+            import :: c_int, c_ptr
+            type(c_ptr),value :: ctx, out
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_diag
          function lbfgsb_hip_qn_draw(ctx,mode,k,seed,first,mean,scale,out,ldo) bind(C,name='lbfgsb_hip_qn_draw') &
             result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
@@ -502,6 +528,42 @@
       integer,intent(out) :: rc
       rc = lbfgsb_hip_qn_diag(ctx, int(mode, c_int), out)
       end subroutine lbfgsb_qn_diag
+
+      ! The model plus a diagonal (include/lbfgsb_hip.h, "The model plus a diagonal"): (B + mu I + diag(d))^-1 on the
+      ! rows that are not pinned.  lbfgsb_qn_shift_set: d is a device buffer of n reals of the context's kind or
+      ! c_null_ptr (D = 0), an entry +inf pins its row; pinned receives the pinned rows of all ranks.  It makes the
+      ! weights and the factor for the pairs of this return: after a return that stores a pair the other three return
+      ! LBFGSB_E_STATE until it is called again.  lbfgsb_qn_shift_solve: out_j = (B + mu I + D)^-1 v_j, k vectors laid
+      ! out as lbfgsb_qn_apply's, +0 on pinned rows.  lbfgsb_qn_shift_logdet: log det of the shifted model on the free
+      ! rows.  lbfgsb_qn_shift_diag: the diagonal of the inverse (n reals), at most 32 stored pairs.
+      subroutine lbfgsb_qn_shift_set(ctx, d, mu, pinned, rc)
+      type(c_ptr),intent(in) :: ctx, d
+      real(c_double),intent(in) :: mu
+      integer(c_int64_t),intent(out) :: pinned
+      integer,intent(out) :: rc
+      pinned = 0
+      rc = lbfgsb_hip_qn_shift_set(ctx, d, mu, pinned)
+      end subroutine lbfgsb_qn_shift_set
+
+      subroutine lbfgsb_qn_shift_solve(ctx, k, v, ldv, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, v, out
+      integer,intent(in) :: k, ldv, ldo
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_solve(ctx, int(k, c_int64_t), v, int(ldv, c_int64_t), out, int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_shift_solve
+
+      subroutine lbfgsb_qn_shift_logdet(ctx, logdet, rc)
+      type(c_ptr),intent(in) :: ctx
+      real(c_double),intent(out) :: logdet
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_logdet(ctx, logdet)
+      end subroutine lbfgsb_qn_shift_logdet
+
+      subroutine lbfgsb_qn_shift_diag(ctx, out, rc)
+      type(c_ptr),intent(in) :: ctx, out
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_diag(ctx, out)
+      end subroutine lbfgsb_qn_shift_diag
 
       ! Square roots, log-determinants and draws of the model (include/lbfgsb_hip.h, same block).  lbfgsb_qn_apply
       ! takes LBFGSB_QN_B_SQRT / LBFGSB_QN_H_SQRT for out_j = A^(1/2) v_j.  lbfgsb_qn_logdet: logdet = log det A over

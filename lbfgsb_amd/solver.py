@@ -509,6 +509,23 @@ class DeviceSolver:
         self._qn_done()
         return out
 
+    def qn_shift(self, d=None, mu: float = 0.0) -> "QnShifted":
+        """The model plus a diagonal, B + mu I + diag(d), as a QnShifted with .solve(v), .logdet(), .diag() and
+        .pinned.  d: an (n,) tensor of this rank's rows or None (D = 0); an entry +inf pins its row -- the row drops
+        out of the matrix, its outputs are +0 -- so d = inf on the rows at bounds gives the model on the free
+        variables.  The weights and the factor of the 2col x 2col K are made here (one pass over d, ceil(2 col / 4)
+        weighted passes over the pairs) and belong to the pairs of this return: after the next return that stores a
+        pair the object raises LbfgsbError ("call qn_shift_set again").  Collective on sharded contexts."""
+        if d is not None:
+            d = self._qn_vec(d, "d")
+            if d.dim() != 1:
+                raise ValueError("d must have shape (n,)")
+        pinned = C.c_int64(0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_shift_set(self.h, None if d is None else d.data_ptr(), float(mu),
+                                               C.byref(pinned)))
+        return QnShifted(self, int(pinned.value), float(mu))
+
     def qn_logpdf(self, x, mean=None, scale: float = 1.0, inverse: bool = True):
         """log N(x_j; mean, scale^2 A) over all rows of all ranks, the covariance A = H (inverse=True, as qn_draw's
         default) or B, for x of shape (n,) or (k, n): the quadratic form of A^-1 by qn_quad's pass and qn_logdet's
@@ -836,6 +853,55 @@ class KktReport:
             + ["%s=%r" % (k, getattr(self, k)) for k in capi.KKT_VAL])
 
 
+class QnShifted:
+    """What DeviceSolver.qn_shift returns: (B + mu I + diag(d))^-1 on the rows that are not pinned, for the pairs of
+    the return it was made at.  `pinned` is the number of pinned rows over all ranks.  The context holds ONE shift:
+    a later qn_shift call replaces the weights this object solves with, and a return that stores a pair makes every
+    method raise LbfgsbError with the library's message."""
+
+    def __init__(self, solver: "DeviceSolver", pinned: int, mu: float):
+        self.solver, self.pinned, self.mu = solver, pinned, mu
+
+    def solve(self, v, out=None):
+        """out = (B + mu I + D)^-1 v for v of shape (n,) or (k, n); pinned rows of out are +0.  Returns out."""
+        s = self.solver
+        v = s._qn_vec(v, "v")
+        if out is None:
+            import torch
+            out = torch.empty(v.shape, dtype=v.dtype, device=v.device)
+        out = s._qn_vec(out, "out")
+        if out.shape != v.shape:
+            raise ValueError("out must have the shape of v")
+        k = 1 if v.dim() == 1 else v.shape[0]
+        ldv = s.n if v.dim() == 1 else v.stride(0)
+        ldo = s.n if out.dim() == 1 else out.stride(0)
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_shift_solve(s.h, k, v.data_ptr(), ldv, out.data_ptr(), ldo))
+        s._qn_done()
+        return out
+
+    def logdet(self) -> float:
+        """log det of B + mu I + D on the free rows of all ranks (no device pass; the same value on every rank)"""
+        val = C.c_double(0.0)
+        check(self.solver.lib.lbfgsb_hip_qn_shift_logdet(self.solver.h, C.byref(val)))
+        return val.value
+
+    def diag(self, out=None):
+        """the diagonal of (B + mu I + D)^-1 as an (n,) tensor, +0 on pinned rows (at most 32 stored pairs)"""
+        import torch
+        s = self.solver
+        if out is None:
+            dt = torch.float32 if s.real == np.float32 else torch.float64
+            out = torch.empty(s.n, dtype=dt, device=torch.device("cuda", s.device))
+        out = s._qn_vec(out, "out")
+        if out.dim() != 1:
+            raise ValueError("out must have shape (n,)")
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_shift_diag(s.h, out.data_ptr()))
+        s._qn_done()
+        return out
+
+
 class QnOperator:
     """The curvature model of a DeviceSolver's last return as a linear operator on this rank's rows: H = B^-1
     (inverse=True, what scipy's L-BFGS-B returns as hess_inv, but starting from the solver's theta) or B.
@@ -865,6 +931,11 @@ class QnOperator:
         if self.root:
             raise ValueError("this operator is a square root already")
         return QnOperator(self.solver, self.inverse, root=True)
+
+    def shifted(self, d=None, mu: float = 0.0) -> "QnShifted":
+        """(B + mu I + diag(d))^-1 as a QnShifted (DeviceSolver.qn_shift): the shift is always added to B, whichever
+        of B and H this operator is"""
+        return self.solver.qn_shift(d=d, mu=mu)
 
     def logdet(self) -> float:
         """log det A over all rows of all ranks (of a root: half of it)"""
