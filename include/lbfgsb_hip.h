@@ -512,8 +512,36 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  * qn_shift_set) solve, logdet and diag return LBFGSB_E_STATE ("call qn_shift_set again"); they never use old weights
  * with new pairs.  When, streams, the collective rule, REAL32 (d, v, out fp32; the weights and every sum fp64) and
  * the refusals are qn_apply's, and the run does not notice the calls.
- * Not offered: the product (B + mu I + D) v -- it is qn_apply(LBFGSB_QN_B) plus an axpy with mu + d --, and roots or
- * draws of the shifted model.
+ * Not offered: the product (B + mu I + D) v -- it is qn_apply(LBFGSB_QN_B) plus an axpy with mu + d.
+ *
+ * Square roots, draws and log-densities of the model plus a diagonal: N(mean, scale^2 Sigma) with Sigma =
+ * (B + mu I + D)^-1 on the free rows -- the Laplace posterior under a Gaussian prior -- sampled and evaluated.  With
+ * the weights w of qn_shift_set and W = [S, Y],
+ *   L = diag(sqrt w) + diag(w) W C W' diag(sqrt w),   L L' = Sigma,
+ * where I + What C What' is the symmetric root of I + What N What', What = diag(sqrt w) W, N the matrix of the solve: C
+ * comes from the weighted Gram that qn_shift_set has reduced, by the host algebra of the square roots above, at the
+ * first of these calls after a qn_shift_set (qn_shift_set itself costs what it did).  L is zero on pinned rows and
+ * columns; it is a factor of Sigma, not its symmetric root.
+ *   qn_shift_sqrt: out_j = L v_j, vectors and results laid out as qn_shift_solve's; pinned rows of out are +0 whatever
+ *     v holds there.  The two passes of qn_shift_solve with other weights, the same bytes.
+ *   qn_shift_draw: out_j = mean + scale L z_(first + j), j < k, z_s the standard normal vector of qn_draw: its entry
+ *     for a row depends on (seed, the global row, s) alone, so the free rows' draws do not move with the rows that are
+ *     pinned, the sharding or k.  A pinned row of out is its mean bit for bit (+0 with mean = NULL).  mean: n_local
+ *     reals or NULL.  Per block of 4 samples one weighted W'z pass and one weighted expansion; z is never stored.
+ *   qn_shift_draw_logpdf: qn_shift_draw -- the same bits in out -- and h_logp[j] = log N(out_j; mean, scale^2 Sigma)
+ *     over the free rows of all ranks, from the z'z over the free rows that the W'z pass carries.
+ *   qn_shift_quad: h_q[j] = (v_j - center)'(B + mu I + D)(v_j - center) over the free rows of all ranks (center:
+ *     n_local reals or NULL); what v and center hold on pinned rows is not used.  One pass per 4 vectors, nothing
+ *     written on the device.
+ *   qn_shift_logpdf: h_logp[j] = log N(x_j; mean, scale^2 Sigma) = -q_j / (2 scale^2) - (nf / 2) log 2 pi - nf log
+ *     |scale| + log det (B + mu I + D) / 2 with nf = n_global - pinned and q_j of qn_shift_quad; the log det is the
+ *     root's (sum log Delta_i - sum log1p(delta_i)), which agrees with qn_shift_logdet to rounding.  With every row
+ *     pinned the log-densities are 0.
+ * h_q and h_logp are host doubles with the same bits on every rank.  At most LBFGSB_QN_ROOT_MAXCOL stored pairs (which
+ * qn_shift_set already demands).  LBFGSB_E_STATE: no shift in force or the pairs have changed ("call qn_shift_set
+ * again"), or the root finds the shifted model not positive definite.  LBFGSB_E_ARG, nothing changed and the shift
+ * still in force: NULL ctx / v / x / out / h_q / h_logp, k < 1, first < 0, ld < n_local, scale 0 or not finite.  When,
+ * streams, the collective rule and REAL32 are qn_shift_solve's, and the run does not notice the calls.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
@@ -543,6 +571,15 @@ int lbfgsb_hip_qn_shift_set(lbfgsb_hip_ctx *ctx, const void *d, double mu, int64
 int lbfgsb_hip_qn_shift_solve(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo);
 int lbfgsb_hip_qn_shift_logdet(lbfgsb_hip_ctx *ctx, double *h_logdet);
 int lbfgsb_hip_qn_shift_diag(lbfgsb_hip_ctx *ctx, void *out);
+int lbfgsb_hip_qn_shift_sqrt(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo);
+int lbfgsb_hip_qn_shift_draw(lbfgsb_hip_ctx *ctx, int64_t k, uint64_t seed, int64_t first, const void *mean,
+                             double scale, void *out, int64_t ldo);
+int lbfgsb_hip_qn_shift_draw_logpdf(lbfgsb_hip_ctx *ctx, int64_t k, uint64_t seed, int64_t first, const void *mean,
+                                    double scale, void *out, int64_t ldo, double *h_logp);
+int lbfgsb_hip_qn_shift_quad(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int64_t ldv, const void *center,
+                             double *h_q);
+int lbfgsb_hip_qn_shift_logpdf(lbfgsb_hip_ctx *ctx, int64_t k, const void *x, int64_t ldx, const void *mean,
+                               double scale, double *h_logp);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.

@@ -70,6 +70,13 @@ PROTOTYPES = {
     "lbfgsb_hip_qn_shift_solve": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
     "lbfgsb_hip_qn_shift_logdet": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "lbfgsb_hip_qn_shift_diag": (C.c_int, [_vp, _vp]),
+    "lbfgsb_hip_qn_shift_sqrt": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
+    "lbfgsb_hip_qn_shift_draw": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int64, _vp, C.c_double, _vp, C.c_int64]),
+    "lbfgsb_hip_qn_shift_draw_logpdf": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int64, _vp, C.c_double, _vp,
+                                                  C.c_int64, C.POINTER(C.c_double)]),
+    "lbfgsb_hip_qn_shift_quad": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(C.c_double)]),
+    "lbfgsb_hip_qn_shift_logpdf": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_double,
+                                             C.POINTER(C.c_double)]),
     "lbfgsb_hip_kkt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "lbfgsb_hip_kkt_list": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp]),
     "lbfgsb_hip_import_state": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -318,6 +318,41 @@ int lbfgsb_hip_qn_shift_diag(lbfgsb_hip_ctx *ctx, void *out) {
   if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_shift_diag: NULL argument");
   return ctx->qn_shift_diag(out);
 }
+int lbfgsb_hip_qn_shift_sqrt(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) {
+  if (!ctx || !v || !out) return fail(LBFGSB_E_ARG, "qn_shift_sqrt: NULL argument");
+  if (k < 1 || ldv < ctx->n || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_shift_sqrt: k < 1 or ld < n_local");
+  return ctx->qn_shift_sqrt(k, v, ldv, out, ldo);
+}
+int lbfgsb_hip_qn_shift_draw(lbfgsb_hip_ctx *ctx, int64_t k, uint64_t seed, int64_t first, const void *mean,
+                             double scale, void *out, int64_t ldo) {
+  if (!ctx || !out) return fail(LBFGSB_E_ARG, "qn_shift_draw: NULL argument");
+  if (k < 1 || first < 0 || ldo < ctx->n)
+    return fail(LBFGSB_E_ARG, "qn_shift_draw: k < 1, first < 0 or ldo < n_local");
+  if (!std::isfinite(scale) || scale == 0.0) return fail(LBFGSB_E_ARG, "qn_shift_draw: scale is 0 or not finite");
+  return ctx->qn_shift_draw(k, seed, first, mean, scale, out, ldo, nullptr);
+}
+int lbfgsb_hip_qn_shift_draw_logpdf(lbfgsb_hip_ctx *ctx, int64_t k, uint64_t seed, int64_t first, const void *mean,
+                                    double scale, void *out, int64_t ldo, double *h_logp) {
+  if (!ctx || !out || !h_logp) return fail(LBFGSB_E_ARG, "qn_shift_draw_logpdf: NULL argument");
+  if (k < 1 || first < 0 || ldo < ctx->n)
+    return fail(LBFGSB_E_ARG, "qn_shift_draw_logpdf: k < 1, first < 0 or ldo < n_local");
+  if (!std::isfinite(scale) || scale == 0.0)
+    return fail(LBFGSB_E_ARG, "qn_shift_draw_logpdf: scale is 0 or not finite");
+  return ctx->qn_shift_draw(k, seed, first, mean, scale, out, ldo, h_logp);
+}
+int lbfgsb_hip_qn_shift_quad(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int64_t ldv, const void *center,
+                             double *h_q) {
+  if (!ctx || !v || !h_q) return fail(LBFGSB_E_ARG, "qn_shift_quad: NULL argument");
+  if (k < 1 || ldv < ctx->n) return fail(LBFGSB_E_ARG, "qn_shift_quad: k < 1 or ldv < n_local");
+  return ctx->qn_shift_quad(k, v, ldv, center, h_q);
+}
+int lbfgsb_hip_qn_shift_logpdf(lbfgsb_hip_ctx *ctx, int64_t k, const void *x, int64_t ldx, const void *mean,
+                               double scale, double *h_logp) {
+  if (!ctx || !x || !h_logp) return fail(LBFGSB_E_ARG, "qn_shift_logpdf: NULL argument");
+  if (k < 1 || ldx < ctx->n) return fail(LBFGSB_E_ARG, "qn_shift_logpdf: k < 1 or ldx < n_local");
+  if (!std::isfinite(scale) || scale == 0.0) return fail(LBFGSB_E_ARG, "qn_shift_logpdf: scale is 0 or not finite");
+  return ctx->qn_shift_logpdf(k, x, ldx, mean, scale, h_logp);
+}
 
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
                    const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,

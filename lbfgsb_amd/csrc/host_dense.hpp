@@ -460,6 +460,27 @@ inline int qn_root(int d, double alpha, const double *g, const double *n_, doubl
   return 0;
 }
 
+// ---- a factor of the model plus a diagonal (lbfgsb_hip_qn_shift_sqrt / _draw / _logpdf) ----
+// Sigma = (B + mu I + D)^-1 = diag(w) + diag(w) W N W' diag(w) on the free rows, W = [S, Y] and N the matrix of
+// qn_shift_coef's map.  With What = diag(w^(1/2)) W: Sigma = w^(1/2) (I + What N What') w^(1/2), and the bracket is
+// qn_root's model at alpha = 1 on the weighted Gram gw = What'What = W' diag(w) W.  Its symmetric root I + What C What'
+// gives L = diag(w^(1/2)) + diag(w) W C W' diag(w^(1/2)) with L L' = Sigma, and
+//   log det (B + mu I + D) on the free rows = sum log Delta_i - *logsum.
+// kf: qn_shift_factor's factor; gw: 2col x 2col, the S block first; cm: C (2col x 2col); work: 7 d^2 + d doubles,
+// d = 2col.  Returns 0, -1 / -2 as qn_root, or qn_shift_coef's info > 0 (a zero pivot in the factor).
+inline int qn_shift_root(int col, double theta, const double *kf, const double *gw, double *cm, double *logsum,
+                         double *work) {
+  *logsum = 0.0;
+  if (col == 0) return 0;
+  const int d = 2 * col;
+  double *nm = work + 6 * (size_t)d * d + d;
+  const int info = qn_nmat(col, [&](const double *stv, const double *ytv, double *cs, double *cy) {
+    return qn_shift_coef(col, theta, kf, stv, ytv, cs, cy);
+  }, nm);
+  if (info) return info;
+  return qn_root(d, 1.0, gw, nm, cm, logsum, work);
+}
+
 // ---- eigenvalues and eigenvectors of the model (lbfgsb_hip_qn_eig / qn_eigvec) ----
 // A = alpha I + W N W' has the eigenvalue alpha + delta_i with the unit eigenvector u_i = W (N P V)_i / delta_i for
 // every delta_i != 0 of qn_spectrum (|u_i|^2 = v_i'(P N P)^2 v_i / delta_i^2 = 1, and A u_i = alpha u_i + W N P

@@ -1,8 +1,10 @@
 // k_qn_common.hpp -- what the kernel files of the curvature-model operator share (k_qn.hip, k_qn_draw.hip,
-// k_qn_shift.hip): the slot of a row in the layout W is in, and the dispatch of a launch over the column capacity MC
-// of a tile, the block of K vectors, the layout (CW), the rows per lane (V) and the cache policy of the loads (NT).
+// k_qn_shift.hip, k_qn_shift_draw.hip): the slot of a row in the layout W is in, the normal deviates of the draws,
+// and the dispatch of a launch over the column capacity MC of a tile, the block of K vectors, the layout (CW), the
+// rows per lane (V) and the cache policy of the loads (NT).
 #pragma once
 #include "kernels_common.hpp"
+#include "philox.hpp"
 
 namespace lbk {
 
@@ -10,6 +12,24 @@ template <bool CW>
 __device__ __forceinline__ int64_t qn_slot(const uint64_t *__restrict__ lmask, int64_t i) {
   if constexpr (CW) return wrow(lmask, i);
   else return i;
+}
+
+// z[kk] = the deviate of (seed, row, s0 + kk), kk < K.  K >= 2: s0 is even.
+template <int K>
+__device__ __forceinline__ void qn_gauss(uint64_t seed, uint64_t row, uint64_t s0, double (&z)[K]) {
+#pragma unroll
+  for (int pp = 0; pp < (K + 1) / 2; ++pp) {
+    double u, v, sn, cs;
+    lbp::uniforms(seed, row, (s0 >> 1) + (uint64_t)pp, u, v);
+    const double r = sqrt(-2.0 * log(u));
+    sincospi(2.0 * v, &sn, &cs);
+    if constexpr (K == 1) {
+      z[0] = (s0 & 1) ? r * sn : r * cs;
+    } else {
+      z[2 * pp] = r * cs;
+      z[2 * pp + 1] = r * sn;
+    }
+  }
 }
 
 namespace {

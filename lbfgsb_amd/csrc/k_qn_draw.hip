@@ -13,27 +13,8 @@
 // sample off), so a block is K / 2 whole pairs.  REAL32: z and all arithmetic in fp64, rounded on store.
 // W is read as it lies (natural order or the tile-local layout through lmask); out and mean are in natural row order.
 #include "k_qn_common.hpp"
-#include "philox.hpp"
 
 namespace lbk {
-
-// z[kk] = the deviate of (seed, row, s0 + kk), kk < K.  K >= 2: s0 is even.
-template <int K>
-__device__ __forceinline__ void qn_gauss(uint64_t seed, uint64_t row, uint64_t s0, double (&z)[K]) {
-#pragma unroll
-  for (int pp = 0; pp < (K + 1) / 2; ++pp) {
-    double u, v, sn, cs;
-    lbp::uniforms(seed, row, (s0 >> 1) + (uint64_t)pp, u, v);
-    const double r = sqrt(-2.0 * log(u));
-    sincospi(2.0 * v, &sn, &cs);
-    if constexpr (K == 1) {
-      z[0] = (s0 & 1) ? r * sn : r * cs;
-    } else {
-      z[2 * pp] = r * cs;
-      z[2 * pp + 1] = r * sn;
-    }
-  }
-}
 
 // sums: slot kk * 2MC + j = S(:, c0 + j)' z_kk, slot kk * 2MC + MC + j = Y(:, c0 + j)' z_kk (qn_wtv_kernel's slots)
 // ZZ: K more sums z_kk'z_kk in the slots 2MC K + kk (lbfgsb_hip_qn_draw_logpdf, the first column tile's launch).  The

@@ -11,6 +11,9 @@
 //                    Gram): qn_wtv's bytes per row plus 8 for w;
 //   qn_shift_expand  out_j = w o (v_j + S cs_j + Y cy_j), coefficients as kernel arguments, nontemporal stores;
 //   qn_shift_diag    out_i = w_i + w_i^2 r_i' N r_i, N packed in LDS as qn_diag packs it.
+// ROOT (a template switch of qn_shift_wtv and qn_shift_expand): the two passes of L v, L = diag(sqrt w) + diag(w) W C
+// W' diag(sqrt w) with L L' = (B + mu I + D)^-1 (lbfgsb_hip_qn_shift_sqrt; section 10g): the sums take the weight
+// sqrt(w_i), and the first tile writes sqrt(w) o v + w o (S cs + Y cy).
 // w is fp64 in both real kinds and, as d, v and out, in natural row order.  W is read in the layout it is in (lmask);
 // none of the kernels writes it.  Reductions: per-lane fp64 accumulators -> block_reduce_store -> qn_finalize.
 // A pinned row's output is +0 by selection, not by multiplication: whatever v holds there, and whatever sign the
@@ -59,8 +62,8 @@ __device__ __forceinline__ void qn_weigh(const double (&wg)[W], double (&x)[W]) 
 }
 
 // sums: slot kk * 2MC + j = S(:, c0 + j)'(w o v_kk), slot kk * 2MC + MC + j = Y(:, c0 + j)'(w o v_kk); VSLOT as in
-// qn_wtv_body (the weights stay in natural order)
-template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT>
+// qn_wtv_body (the weights stay in natural order).  ROOT: sqrt(w) in place of w
+template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT, bool ROOT>
 __global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, const T *__restrict__ ws,
                                                              const T *__restrict__ wy, const T *__restrict__ zero,
                                                              int64_t ldw, int m, int head, int col, int c0,
@@ -84,6 +87,10 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, const T 
       ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
       ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
     }
+    if constexpr (ROOT) {
+#pragma unroll
+      for (int w = 0; w < W; ++w) wg[w] = sqrt(wg[w]);
+    }
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) qn_weigh<W>(wg, vv[kk]);
 #pragma unroll
@@ -101,7 +108,8 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, const T 
 
 // first: out_kk[i] = w_i (src_kk[i] + sum_j cf.c[kk][j] S(i, c0 + j) + cf.c[kk][MC + j] Y(i, c0 + j));
 // else (a later column tile, src = out): out_kk[i] = src_kk[i] + w_i (the sum)
-template <typename T, int MC, int K, int V, bool CW, bool NT>
+// ROOT, first: out_kk[i] = sqrt(w_i) src_kk[i] + w_i (the sum), +0 where w_i = 0; the later tiles as above
+template <typename T, int MC, int K, int V, bool CW, bool NT, bool ROOT>
 __global__ __launch_bounds__(BLOCK) void qn_shift_expand_kernel(int64_t n, const T *__restrict__ ws,
                                                                 const T *__restrict__ wy, const T *__restrict__ zero,
                                                                 int64_t ldw, int m, int head, int col, int c0,
@@ -127,7 +135,7 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_expand_kernel(int64_t n, const
       double o[W];
 #pragma unroll
       for (int w = 0; w < W; ++w) {
-        double e = first ? x[kk][w] : 0.0;
+        double e = first && !ROOT ? x[kk][w] : 0.0;
 #pragma unroll
         for (int j = 0; j < MC; ++j) {
           e += cf.c[kk][j] * a[j][w];
@@ -139,6 +147,9 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_expand_kernel(int64_t n, const
       if (!first) {
 #pragma unroll
         for (int w = 0; w < W; ++w) o[w] += x[kk][w];
+      } else if constexpr (ROOT) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) o[w] = wg[w] == 0.0 ? 0.0 : sqrt(wg[w]) * x[kk][w] + o[w];
       }
       stnt<W>(out.p[kk] + i, o);
     }
@@ -200,39 +211,40 @@ hipError_t launch_qn_shift_w(const Queue &q, int64_t n, const T *d, double shift
 
 template <typename T>
 hipError_t launch_qn_shift_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                               QnVecs<T> v, bool vslot, const double *wgt, double *part, double *res) {
-  if (!qn_block_ok(mc, k)) return hipErrorInvalidValue;
+                               QnVecs<T> v, bool vslot, bool root, const double *wgt, double *part, double *res) {
+  if (!qn_block_ok(mc, k) || (vslot && root)) return hipErrorInvalidValue;
   // (two rows per lane where qn_wtv has them; the weights add 2 V registers to its operands)
   bool vec2 = !vslot && 2 * mc * k <= 20 && aligned_for(wgt, 2);
   for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
   int g = 0;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT,
-      QN_DISPATCH_BOOL(vslot, VS, {
-    if constexpr (!VS || V == 1) {
-      auto kern = qn_shift_wtv_kernel<T, MC, K, V, CW, VS, NT>;
+      QN_DISPATCH_BOOL(vslot, VS, QN_DISPATCH_BOOL(root, ROOT, {
+    if constexpr ((!VS || V == 1) && !(VS && ROOT)) {
+      auto kern = qn_shift_wtv_kernel<T, MC, K, V, CW, VS, NT, ROOT>;
       g = grid_for_w(q, n, V, (const void *)kern);
       hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
                          w.lmask, v, wgt, part);
     }
-  })))));
+  }))))));
   return launch_qn_finalize(q, part, g, 2 * mc * k, res);
 }
 
 template <typename T>
 hipError_t launch_qn_shift_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                                  const double *coef, QnVecs<T> src, const double *wgt, bool first, QnOuts<T> out) {
+                                  const double *coef, QnVecs<T> src, const double *wgt, bool first, bool root,
+                                  QnOuts<T> out) {
   if (!qn_block_ok(mc, k)) return hipErrorInvalidValue;
   bool vec2 = 2 * mc * k <= 20 && aligned_for(wgt, 2);
   for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(src.p[kk], 2) && aligned_for((const T *)out.p[kk], 2);
   bool done = false;
-  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
+  QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, QN_DISPATCH_BOOL(root, ROOT, {
     const QnCoef<MC, K> cf = qn_coef_args<MC, K>(coef, 1.0);
-    auto kern = qn_shift_expand_kernel<T, MC, K, V, CW, NT>;
+    auto kern = qn_shift_expand_kernel<T, MC, K, V, CW, NT, ROOT>;
     const int g = grid_for_w(q, n, V, (const void *)kern);
     hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
                        w.lmask, cf, src, wgt, first ? 1 : 0, out);
     done = true;
-  }))));
+  })))));
   if (!done) return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -259,9 +271,10 @@ hipError_t launch_qn_shift_diag(const Queue &q, int64_t n, WStore<T> w, int head
   template hipError_t launch_qn_shift_w<T>(const Queue &, int64_t, const T *, double, double *, double *,         \
                                            double *);                                                             \
   template hipError_t launch_qn_shift_wtv<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,          \
-                                             QnVecs<T>, bool, const double *, double *, double *);                \
+                                             QnVecs<T>, bool, bool, const double *, double *, double *);          \
   template hipError_t launch_qn_shift_expand<T>(const Queue &, int64_t, WStore<T>, int, int, int, int, int,       \
-                                                const double *, QnVecs<T>, const double *, bool, QnOuts<T>);      \
+                                                const double *, QnVecs<T>, const double *, bool, bool,            \
+                                                QnOuts<T>);                                                       \
   template hipError_t launch_qn_shift_diag<T>(const Queue &, int64_t, WStore<T>, int, int, const double *,        \
                                               const double *, T *);
 QN_SHIFT_INST(double)

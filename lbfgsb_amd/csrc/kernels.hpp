@@ -573,19 +573,39 @@ constexpr int QN_SHIFT_SUMS = 3;
 template <typename T>
 hipError_t launch_qn_shift_w(const Queue &q, int64_t n, const T *d, double shift, double *wgt, double *part,
                              double *res);
-// launch_qn_wtv's plain pass on wgt o v_k (vslot: the vectors are columns of W, the weights still natural)
+// launch_qn_wtv's plain pass on wgt o v_k (vslot: the vectors are columns of W, the weights still natural); root: on
+// sqrt(wgt) o v_k (not with vslot)
 template <typename T>
 hipError_t launch_qn_shift_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                               QnVecs<T> v, bool vslot, const double *wgt, double *part, double *res);
+                               QnVecs<T> v, bool vslot, bool root, const double *wgt, double *part, double *res);
 // first: out_k = wgt o (src_k + [S, Y](:, tile) coef[k * 2 mc ...]); else out_k = src_k + wgt o ([S, Y] coef) (src_k
-// is out_k: the second and later tiles).  Rows with wgt = 0 of a first tile are +0 whatever src holds there
+// is out_k: the second and later tiles).  Rows with wgt = 0 of a first tile are +0 whatever src holds there.  root: a
+// first tile writes sqrt(wgt) o src_k + wgt o ([S, Y] coef)
 template <typename T>
 hipError_t launch_qn_shift_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
-                                  const double *coef, QnVecs<T> src, const double *wgt, bool first, QnOuts<T> out);
+                                  const double *coef, QnVecs<T> src, const double *wgt, bool first, bool root,
+                                  QnOuts<T> out);
 // out_i = wgt_i + wgt_i^2 r_i' N r_i (col <= 32; np as launch_qn_diag takes it)
 template <typename T>
 hipError_t launch_qn_shift_diag(const Queue &q, int64_t n, WStore<T> w, int head, int col, const double *np,
                                 const double *wgt, T *out);
+// Draws and densities of the model plus a diagonal (k_qn_shift_draw.hip): launch_qn_wtz / _draw / _wtv's centred pass
+// with the weights.  wtz: the sums of sqrt(wgt) o z_k; zz: k more, z_k'z_k over the rows with wgt != 0
+template <typename T>
+hipError_t launch_qn_shift_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                               uint64_t seed, int64_t row0, int64_t s0, bool zz, const double *wgt, double *part,
+                               double *res);
+// first: out_k = mean + alpha sqrt(wgt) o z_k + wgt o ([S, Y](:, tile) coef[k * 2 mc ...]) (mean may be NULL), the
+// mean itself (+0 without one) where wgt = 0; else out_k += wgt o ([S, Y] coef)
+template <typename T>
+hipError_t launch_qn_shift_draw(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                                const double *coef, double alpha, uint64_t seed, int64_t row0, int64_t s0,
+                                bool first, const T *mean, const double *wgt, QnOuts<T> out);
+// the sums of f o (v_k - center), f = (wgt != 0) (center may be NULL); dd: k more in res[2 mc k + kk], the sums of
+// (v_k - center)^2 / wgt over the rows with wgt != 0
+template <typename T>
+hipError_t launch_qn_shift_wtd(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                               QnVecs<T> v, const T *center, bool dd, const double *wgt, double *part, double *res);
 
 // The basis pass (k_qn_eig.hip): out_j (+)= [S, Y](:, tile) coef[j * 2 mc ...] for ALL j < k <= QN_BASIS_KMAX in one
 // launch, output j at out + j * ldo; the tile's columns are read once per row.  acc: add to what out holds (the tiles

@@ -174,6 +174,12 @@ struct lbfgsb_hip_ctx {
   virtual int qn_shift_solve(int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) = 0;
   virtual int qn_shift_logdet(double *h_logdet) = 0;
   virtual int qn_shift_diag(void *out) = 0;
+  virtual int qn_shift_sqrt(int64_t k, const void *v, int64_t ldv, void *out, int64_t ldo) = 0;
+  virtual int qn_shift_draw(int64_t k, uint64_t seed, int64_t first, const void *mean, double scale, void *out,
+                            int64_t ldo, double *h_logp) = 0;  // (h_logp may be NULL: the draws alone)
+  virtual int qn_shift_quad(int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) = 0;
+  virtual int qn_shift_logpdf(int64_t k, const void *x, int64_t ldx, const void *mean, double scale,
+                              double *h_logp) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

@@ -4,7 +4,8 @@
 // symmetric square roots, log-determinants and draws (lbfgsb_hip_qn_logdet, lbfgsb_hip_qn_draw; k_qn_draw.hip), and
 // quadratic forms and Gaussian log-densities (lbfgsb_hip_qn_quad, qn_logpdf, qn_draw_logpdf),
 // and Gram matrices on blocks of vectors (lbfgsb_hip_qn_gram; section 10d), and solves, log-determinants and diagonals
-// of the model plus a diagonal (lbfgsb_hip_qn_shift_*; k_qn_shift.hip, section 10f).
+// of the model plus a diagonal (lbfgsb_hip_qn_shift_*; k_qn_shift.hip, section 10f), and its square roots, draws and
+// log-densities (lbfgsb_hip_qn_shift_sqrt / _draw / _quad / _logpdf; k_qn_shift_draw.hip, section 10g).
 // Which launches a pass over W is made of and where their sums land is decided in one place, qn_plan.hpp (host-only,
 // walked on the CPU by tests/qn_plan_check.cpp): every W'V pass here goes through qn_sums_by on a plan, every
 // expansion through qn_expand_by, and a new operator hooks in with a plan and a launch of its own.
@@ -599,7 +600,12 @@
     int64_t gen = -1;            // the pair generation the weights and the factor were made at
     int64_t pinned = 0;          // rows with d_i = +inf, all ranks
     double logdet = 0.0;         // log det of the shifted model on the free rows
+    double sumlog = 0.0;         // the sum of log Delta_i over the free rows, all ranks
     std::vector<double> kf;      // qn_shift_factor's factor of K (2col x 2col)
+    std::vector<double> gw;      // the weighted Gram [S, Y]' diag(w) [S, Y] the factor was made from
+    int64_t root_gen = -1;       // the pair generation of the root below; -1 after every qn_shift_set (made at its
+    std::vector<double> root_c;  // first use: host_dense.hpp, qn_shift_root): C of L = w^1/2 + w W C W' w^1/2
+    double root_logsum = 0.0;    // sum log Delta - log det of the shifted model, by the root's route
     double *d_w[2] = {nullptr, nullptr};  // the weights (n doubles, natural order); a set that is refused leaves the
     int cur = 0;                          // live ones alone: it writes the other buffer, and success swaps
     double *d_n = nullptr;       // qn_shift_diag's packed N
@@ -647,7 +653,7 @@
       CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::None), sums.data(), nullptr, [&](const lbk::QnPiece &p) {
         lbk::QnVecs<T> vv{};
         for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
-        return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, true, wgt,
+        return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, true, false, wgt,
                                                        qn.d_part, qn.d_res + p.off),
                            "qn_shift_wtv");
       }));
@@ -679,10 +685,10 @@
     if (bad > 0.0)
       return fail(LBFGSB_E_ARG, "qn_shift_set: theta + mu + d_i <= 0 or NaN on " + std::to_string((long long)bad) +
                                     " rows");
-    std::vector<double> kf((size_t)d * d + 1), km((size_t)d * d + 1);
+    std::vector<double> kf((size_t)d * d + 1), km((size_t)d * d + 1), gw((size_t)d * d);
     double ldk = 0.0, ldm = 0.0;
     if (col > 0) {
-      std::vector<double> gw((size_t)d * d), sts, syl;
+      std::vector<double> sts, syl;
       CHK(qn_shift_minv(sts, syl));
       CHK(qn_shift_gram(wgt, gw.data()));
       if (lbh::qn_shift_factor(col, qn.theta, syl.data(), col, sts.data(), col, nullptr, km.data(), &ldm))
@@ -690,7 +696,8 @@
       if (lbh::qn_shift_factor(col, qn.theta, syl.data(), col, sts.data(), col, gw.data(), kf.data(), &ldk))
         return fail(LBFGSB_E_STATE, "qn_shift_set: the shifted model is not positive definite on the free rows");
     }
-    qsh.kf.swap(kf);
+    qsh.kf.swap(kf), qsh.gw.swap(gw);
+    qsh.root_gen = -1, qsh.sumlog = sumlog;
     qsh.logdet = sumlog + (ldk - ldm);
     qsh.pinned = (int64_t)pinned;
     qsh.cur = dst, qsh.gen = qn.gen, qsh.have = true, qsh.n_ok = false;
@@ -708,6 +715,11 @@
   int qn_shift_solve(int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) override {
     CHK(qn_ready());
     CHK(qn_shift_live());
+    return qn_shift_apply(false, k, v_, ldv, out_, ldo);
+  }
+  // root: out_j = L v_j = sqrt(w) o v_j + w o (S cs_j + Y cy_j), (cs; cy) = C [S'(sqrt(w) o v_j); Y'(sqrt(w) o v_j)] --
+  // the same two passes with the root's weights
+  int qn_shift_apply(bool root, int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) {
     const int col = qn.col;
     const lbk::WStore<T> w = Wc();
     const double *wgt = qsh.d_w[qsh.cur];
@@ -722,14 +734,15 @@
         CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::None), sums.data(), nullptr, [&](const lbk::QnPiece &p) {
           lbk::QnVecs<T> vv{};
           for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = vp[p.k0 + kk];
-          return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, false, wgt,
+          return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, false, root, wgt,
                                                          qn.d_part, qn.d_res + p.off),
                              "qn_shift_wtv");
         }));
         for (int kk = 0; kk < kc; ++kk) {
           const double *sv = sums.data() + (size_t)kk * 2 * col;
           double *c = cf.data() + (size_t)kk * 2 * col;
-          if (lbh::qn_shift_coef(col, qn.theta, qsh.kf.data(), sv, sv + col, c, c + col))
+          if (root) qn_shift_root_map(1.0, sv, c);
+          else if (lbh::qn_shift_coef(col, qn.theta, qsh.kf.data(), sv, sv + col, c, c + col))
             return fail(LBFGSB_E_STATE, "qn_shift_solve: a zero pivot in the factor of K");
         }
       }
@@ -741,7 +754,7 @@
           src.p[kk] = p.c0 == 0 ? vp[p.k0 + kk] : dst.p[kk];
         }
         return qn_launched(lbk::launch_qn_shift_expand<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef, src, wgt,
-                                                          p.c0 == 0, dst),
+                                                          p.c0 == 0, root, dst),
                            "qn_shift_expand");
       }));
     }
@@ -770,6 +783,140 @@
     CHK(qn_launched(lbk::launch_qn_shift_diag<T>(q, n, Wc(), qn.head, col, qsh.d_n, qsh.d_w[qsh.cur], (T *)out_),
                     "qn_shift_diag"));
     return qn_finish();
+  }
+
+  // ---- square roots, draws and log-densities of the model plus a diagonal.  With Sigma =
+  // (B + mu I + D)^-1 on the free rows: L = diag(sqrt w) + diag(w) W C W' diag(sqrt w), L L' = Sigma, C from
+  // qn_shift_root on the weighted Gram that qn_shift_set reduced -- host algebra only, at the first use after a set.
+  // (more than 64 pairs: LBFGSB_E_ARG, as every root -- before the shift is asked for, which qn_shift_set refuses
+  //  there)
+  int qn_shift_root_coef() {
+    const int col = qn.col, d = 2 * col;
+    if (col > LBFGSB_QN_ROOT_MAXCOL) return fail(LBFGSB_E_ARG, "qn_shift: a root of more than 64 stored pairs");
+    CHK(qn_shift_live());
+    if (qsh.root_gen == qsh.gen) return 0;
+    std::vector<double> cm((size_t)d * d + 1), work((size_t)7 * d * d + d + 1);
+    double logsum = 0.0;
+    const int rc = lbh::qn_shift_root(col, qn.theta, qsh.kf.data(), qsh.gw.data(), cm.data(), &logsum, work.data());
+    if (rc == -2) return fail(LBFGSB_E_STATE, "qn_shift: the shifted model is not positive definite on the free rows");
+    if (rc < 0) return fail(LBFGSB_E_STATE, "qn_shift: the eigensolver of the root did not converge");
+    if (rc) return fail(LBFGSB_E_STATE, "qn_shift: a zero pivot in the factor of K");
+    qsh.root_c.swap(cm);
+    qsh.root_logsum = logsum, qsh.root_gen = qsh.gen;
+    return 0;
+  }
+  // c = f C sums for one vector (sums = [S'(sqrt(w) o v); Y'(sqrt(w) o v)])
+  void qn_shift_root_map(double f, const double *sums, double *c) const {
+    const int d = 2 * qn.col;
+    const double *cm = qsh.root_c.data();
+    for (int i = 0; i < d; ++i) {
+      double t = 0.0;
+      for (int j = 0; j < d; ++j) t = t + cm[i + (size_t)j * d] * sums[j];
+      c[i] = f * t;
+    }
+  }
+  // the free rows of all ranks, and nf log 2 pi + 2 nf log |scale| - log det (B + mu I + D) by the root's route (after
+  // qn_shift_root_coef): -2 x the constant of a log-density under N(mean, scale^2 Sigma)
+  double qn_shift_free() const { return (double)(nglob - qsh.pinned); }
+  double qn_shift_log_norm(double scale) const {
+    const double nf = qn_shift_free();
+    return nf * std::log(6.283185307179586476925) + 2.0 * nf * std::log(std::fabs(scale)) -
+           (qsh.sumlog - qsh.root_logsum);
+  }
+  int qn_shift_sqrt(int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) override {
+    CHK(qn_ready());
+    CHK(qn_shift_root_coef());
+    return qn_shift_apply(true, k, v_, ldv, out_, ldo);
+  }
+  // out_j = mean + scale L z_(first + j): per block of samples the weighted W'z sums, c = scale C sums on the host,
+  // then the weighted expansion with z generated again.  h_logp (k values) or NULL: the log-density of every draw under
+  // N(mean, scale^2 Sigma) on the free rows, from the z'z over them that the W'z pass carries
+  int qn_shift_draw(int64_t k, uint64_t seed, int64_t first, const void *mean_, double scale, void *out_, int64_t ldo,
+                    double *h_logp) override {
+    CHK(qn_ready());
+    CHK(qn_shift_root_coef());
+    const int col = qn.col;
+    const double lconst = h_logp ? qn_shift_log_norm(scale) : 0.0;
+    const bool none_free = nglob == qsh.pinned;
+    double zz[lbk::QN_KMAX];
+    const lbk::WStore<T> w = Wc();
+    const double *wgt = qsh.d_w[qsh.cur];
+    const T *mean = (const T *)mean_;
+    T *out = (T *)out_;
+    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf(sums.size());
+    for (int64_t k0 = 0; k0 < k;) {
+      const int64_t s0 = first + k0;
+      const int kc = (s0 & 1) ? 1 : (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
+      if (col > 0 || h_logp) {
+        CHK(qn_sums_by(lbk::qn_plan(col, kc, h_logp ? QnCarry::Norms : QnCarry::None), sums.data(), zz,
+                       [&](const lbk::QnPiece &p) {
+          return qn_launched(lbk::launch_qn_shift_wtz<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, seed, row0,
+                                                         s0 + p.k0, p.carry == QnCarry::Norms, wgt, qn.d_part,
+                                                         qn.d_res + p.off),
+                             "qn_shift_wtz");
+        }));
+        for (int kk = 0; kk < kc && col > 0; ++kk)
+          qn_shift_root_map(scale, sums.data() + (size_t)kk * 2 * col, cf.data() + (size_t)kk * 2 * col);
+        for (int kk = 0; kk < kc && h_logp; ++kk) h_logp[k0 + kk] = none_free ? 0.0 : -0.5 * (lconst + zz[kk]);
+      }
+      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
+        lbk::QnOuts<T> dst{};
+        for (int kk = 0; kk < p.k; ++kk) dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
+        return qn_launched(lbk::launch_qn_shift_draw<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef, scale, seed, row0,
+                                                        s0 + p.k0, p.c0 == 0, mean, wgt, dst),
+                           "qn_shift_draw");
+      }));
+      k0 += kc;
+    }
+    return qn_finish();
+  }
+  // q_j = (v_j - center)'(B + mu I + D)(v_j - center) on the free rows = sum Delta_i q_i^2 + t'N_B t with
+  // t = [S, Y]'(f o q): qn_quad's route for B with the Delta-weighted squared norm in place of theta q'q, one pass and
+  // nothing written
+  int qn_shift_quad_by(int64_t k, const T *v, int64_t ldv, const T *center, double *h_q) {
+    const int col = qn.col;
+    if (col > 0 && qn.theta_gram) CHK(qn_gram());
+    const std::vector<double> dg = qn_dg();
+    const lbk::WStore<T> w = Wc();
+    const double *wgt = qsh.d_w[qsh.cur];
+    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), c((size_t)2 * std::max(col, 1));
+    double dd[lbk::QN_KMAX];
+    for (int64_t k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
+      const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
+      CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::Norms), sums.data(), dd, [&](const lbk::QnPiece &p) {
+        lbk::QnVecs<T> vv{};
+        for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v + (k0 + p.k0 + kk) * ldv;
+        return qn_launched(lbk::launch_qn_shift_wtd<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, center,
+                                                       p.carry == QnCarry::Norms, wgt, qn.d_part, qn.d_res + p.off),
+                           "qn_shift_wtd");
+      }));
+      for (int kk = 0; kk < kc; ++kk) {
+        const double *sv = sums.data() + (size_t)kk * 2 * col;
+        double t = 0.0;  // t'(N_B t), S part then Y part, ascending
+        if (col > 0) {
+          CHK(qn_coef(false, dg.data(), sv, sv + col, c.data(), c.data() + col));
+          for (int i = 0; i < 2 * col; ++i) t = t + sv[i] * c[(size_t)i];
+        }
+        h_q[k0 + kk] = dd[kk] + t;
+      }
+    }
+    return 0;
+  }
+  int qn_shift_quad(int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) override {
+    CHK(qn_ready());
+    CHK(qn_shift_live());
+    return qn_shift_quad_by(k, (const T *)v, ldv, (const T *)center, h_q);
+  }
+  // log N(x_j; mean, scale^2 Sigma) on the free rows: the quadratic form above, log det by the root's route
+  int qn_shift_logpdf(int64_t k, const void *x, int64_t ldx, const void *mean, double scale,
+                      double *h_logp) override {
+    CHK(qn_ready());
+    CHK(qn_shift_root_coef());
+    const double lconst = qn_shift_log_norm(scale);
+    CHK(qn_shift_quad_by(k, (const T *)x, ldx, (const T *)mean, h_logp));
+    for (int64_t j = 0; j < k; ++j)
+      h_logp[j] = nglob == qsh.pinned ? 0.0 : -0.5 * (lconst + h_logp[j] / (scale * scale));
+    return 0;
   }
 
   int qn_finish() {

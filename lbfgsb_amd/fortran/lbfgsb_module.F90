@@ -51,6 +51,8 @@
       public :: lbfgsb_qn_gram                          ! the k x k matrix (V - center)' A (V - center)
       public :: lbfgsb_qn_eig, lbfgsb_qn_eigvec         ! eigenvalues and unit eigenvectors of B or H
       public :: lbfgsb_qn_shift_set, lbfgsb_qn_shift_solve, lbfgsb_qn_shift_logdet, lbfgsb_qn_shift_diag
+      public :: lbfgsb_qn_shift_sqrt, lbfgsb_qn_shift_draw, lbfgsb_qn_shift_draw_logpdf   ! its factor and draws
+      public :: lbfgsb_qn_shift_quad, lbfgsb_qn_shift_logpdf                              ! ... and densities
                                                        ! solves, log det and diagonal of (B + mu I + diag(d))^-1
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
                                                        ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
@@ -193,6 +195,45 @@
             type(c_ptr),value :: ctx, out
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_shift_diag
+         function lbfgsb_hip_qn_shift_sqrt(ctx,k,v,ldv,out,ldo) bind(C,name='lbfgsb_hip_qn_shift_sqrt') result(rc)
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, v, out
+            integer(c_int64_t),value :: k, ldv, ldo
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_sqrt
+         function lbfgsb_hip_qn_shift_draw(ctx,k,seed,first,mean,scale,out,ldo) &
+            bind(C,name='lbfgsb_hip_qn_shift_draw') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, mean, out
+            integer(c_int64_t),value :: k, seed, first, ldo
+            real(c_double),value :: scale
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_draw
+         function lbfgsb_hip_qn_shift_draw_logpdf(ctx,k,seed,first,mean,scale,out,ldo,logp) &
+            bind(C,name='lbfgsb_hip_qn_shift_draw_logpdf') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, mean, out
+            integer(c_int64_t),value :: k, seed, first, ldo
+            real(c_double),value :: scale
+            real(c_double) :: logp(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_draw_logpdf
+         function lbfgsb_hip_qn_shift_quad(ctx,k,v,ldv,center,q) bind(C,name='lbfgsb_hip_qn_shift_quad') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, v, center
+            integer(c_int64_t),value :: k, ldv
+            real(c_double) :: q(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_quad
+         function lbfgsb_hip_qn_shift_logpdf(ctx,k,x,ldx,mean,scale,logp) bind(C,name='lbfgsb_hip_qn_shift_logpdf') &
+            result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, x, mean
+            integer(c_int64_t),value :: k, ldx
+            real(c_double),value :: scale
+            real(c_double) :: logp(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_logpdf
          function lbfgsb_hip_qn_draw(ctx,mode,k,seed,first,mean,scale,out,ldo) bind(C,name='lbfgsb_hip_qn_draw') &
             result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
@@ -564,6 +605,59 @@
       integer,intent(out) :: rc
       rc = lbfgsb_hip_qn_shift_diag(ctx, out)
       end subroutine lbfgsb_qn_shift_diag
+
+      ! Square roots, draws and log-densities of the model plus a diagonal (include/lbfgsb_hip.h, "Square roots, draws
+      ! and log-densities of the model plus a diagonal"): N(mean, scale^2 Sigma), Sigma = (B + mu I + D)^-1 on the free
+      ! rows, after lbfgsb_qn_shift_set and under its staleness rule.  lbfgsb_qn_shift_sqrt: out_j = L v_j with L L' =
+      ! Sigma, laid out as lbfgsb_qn_shift_solve's.  lbfgsb_qn_shift_draw: out_j = mean + scale L z_(first + j), j < k,
+      ! z as lbfgsb_qn_draw's (mean may be c_null_ptr); a pinned row is its mean.  lbfgsb_qn_shift_draw_logpdf: the same
+      ! draws and logp(j) = their log-densities.  lbfgsb_qn_shift_quad: q(j) = (v_j - center)'(B + mu I + D)(v_j -
+      ! center) on the free rows.  lbfgsb_qn_shift_logpdf: logp(j) = log N(x_j; mean, scale^2 Sigma).  q and logp are
+      ! host arrays, complete over the rows of all ranks; scale /= 0.
+      subroutine lbfgsb_qn_shift_sqrt(ctx, k, v, ldv, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, v, out
+      integer,intent(in) :: k, ldv, ldo
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_sqrt(ctx, int(k, c_int64_t), v, int(ldv, c_int64_t), out, int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_shift_sqrt
+
+      subroutine lbfgsb_qn_shift_draw(ctx, k, seed, first, mean, scale, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, mean, out
+      integer,intent(in) :: k, first, ldo
+      integer(c_int64_t),intent(in) :: seed
+      real(c_double),intent(in) :: scale
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_draw(ctx, int(k, c_int64_t), seed, int(first, c_int64_t), mean, scale, out, &
+                                    int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_shift_draw
+
+      subroutine lbfgsb_qn_shift_draw_logpdf(ctx, k, seed, first, mean, scale, out, ldo, logp, rc)
+      type(c_ptr),intent(in) :: ctx, mean, out
+      integer,intent(in) :: k, first, ldo
+      integer(c_int64_t),intent(in) :: seed
+      real(c_double),intent(in) :: scale
+      real(c_double),intent(out) :: logp(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_draw_logpdf(ctx, int(k, c_int64_t), seed, int(first, c_int64_t), mean, scale, out, &
+                                           int(ldo, c_int64_t), logp)
+      end subroutine lbfgsb_qn_shift_draw_logpdf
+
+      subroutine lbfgsb_qn_shift_quad(ctx, k, v, ldv, center, q, rc)
+      type(c_ptr),intent(in) :: ctx, v, center
+      integer,intent(in) :: k, ldv
+      real(c_double),intent(out) :: q(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_quad(ctx, int(k, c_int64_t), v, int(ldv, c_int64_t), center, q)
+      end subroutine lbfgsb_qn_shift_quad
+
+      subroutine lbfgsb_qn_shift_logpdf(ctx, k, x, ldx, mean, scale, logp, rc)
+      type(c_ptr),intent(in) :: ctx, x, mean
+      integer,intent(in) :: k, ldx
+      real(c_double),intent(in) :: scale
+      real(c_double),intent(out) :: logp(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_logpdf(ctx, int(k, c_int64_t), x, int(ldx, c_int64_t), mean, scale, logp)
+      end subroutine lbfgsb_qn_shift_logpdf
 
       ! Square roots, log-determinants and draws of the model (include/lbfgsb_hip.h, same block).  lbfgsb_qn_apply
       ! takes LBFGSB_QN_B_SQRT / LBFGSB_QN_H_SQRT for out_j = A^(1/2) v_j.  lbfgsb_qn_logdet: logdet = log det A over

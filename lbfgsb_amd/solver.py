@@ -510,8 +510,8 @@ class DeviceSolver:
         return out
 
     def qn_shift(self, d=None, mu: float = 0.0) -> "QnShifted":
-        """The model plus a diagonal, B + mu I + diag(d), as a QnShifted with .solve(v), .logdet(), .diag() and
-        .pinned.  d: an (n,) tensor of this rank's rows or None (D = 0); an entry +inf pins its row -- the row drops
+        """The model plus a diagonal, B + mu I + diag(d), as a QnShifted with .solve(v), .logdet(), .diag(), .pinned,
+        and .sqrt(v), .sample(k, seed), .quad(v), .log_prob(x) of N(mean, scale^2 (B + mu I + diag(d))^-1).  d: an (n,) tensor of this rank's rows or None (D = 0); an entry +inf pins its row -- the row drops
         out of the matrix, its outputs are +0 -- so d = inf on the rows at bounds gives the model on the free
         variables.  The weights and the factor of the 2col x 2col K are made here (one pass over d, ceil(2 col / 4)
         weighted passes over the pairs) and belong to the pairs of this return: after the next return that stores a
@@ -855,7 +855,9 @@ class KktReport:
 
 class QnShifted:
     """What DeviceSolver.qn_shift returns: (B + mu I + diag(d))^-1 on the rows that are not pinned, for the pairs of
-    the return it was made at.  `pinned` is the number of pinned rows over all ranks.  The context holds ONE shift:
+    the return it was made at, and the Gaussian N(mean, scale^2 (B + mu I + diag(d))^-1) on them: solve / logdet / diag,
+    and sqrt / sample / quad / log_prob.  `pinned` is the number of pinned rows over all ranks.  The context holds ONE
+    shift:
     a later qn_shift call replaces the weights this object solves with, and a return that stores a pair makes every
     method raise LbfgsbError with the library's message."""
 
@@ -864,21 +866,7 @@ class QnShifted:
 
     def solve(self, v, out=None):
         """out = (B + mu I + D)^-1 v for v of shape (n,) or (k, n); pinned rows of out are +0.  Returns out."""
-        s = self.solver
-        v = s._qn_vec(v, "v")
-        if out is None:
-            import torch
-            out = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-        out = s._qn_vec(out, "out")
-        if out.shape != v.shape:
-            raise ValueError("out must have the shape of v")
-        k = 1 if v.dim() == 1 else v.shape[0]
-        ldv = s.n if v.dim() == 1 else v.stride(0)
-        ldo = s.n if out.dim() == 1 else out.stride(0)
-        s.wait_stream()
-        check(s.lib.lbfgsb_hip_qn_shift_solve(s.h, k, v.data_ptr(), ldv, out.data_ptr(), ldo))
-        s._qn_done()
-        return out
+        return self._apply(self.solver.lib.lbfgsb_hip_qn_shift_solve, v, out)
 
     def logdet(self) -> float:
         """log det of B + mu I + D on the free rows of all ranks (no device pass; the same value on every rank)"""
@@ -900,6 +888,90 @@ class QnShifted:
         check(s.lib.lbfgsb_hip_qn_shift_diag(s.h, out.data_ptr()))
         s._qn_done()
         return out
+
+    def _apply(self, entry, v, out):
+        s = self.solver
+        v = s._qn_vec(v, "v")
+        if out is None:
+            import torch
+            out = torch.empty(v.shape, dtype=v.dtype, device=v.device)
+        out = s._qn_vec(out, "out")
+        if out.shape != v.shape:
+            raise ValueError("out must have the shape of v")
+        k = 1 if v.dim() == 1 else v.shape[0]
+        ldv = s.n if v.dim() == 1 else v.stride(0)
+        ldo = s.n if out.dim() == 1 else out.stride(0)
+        s.wait_stream()
+        check(entry(s.h, k, v.data_ptr(), ldv, out.data_ptr(), ldo))
+        s._qn_done()
+        return out
+
+    def sqrt(self, v, out=None):
+        """out = L v for v of shape (n,) or (k, n), L L' = (B + mu I + D)^-1 on the free rows: L = diag(sqrt w) +
+        diag(w) [S, Y] C [S, Y]' diag(sqrt w), a factor of the covariance (not its symmetric root), zero on pinned
+        rows and columns; pinned rows of out are +0.  With v standard normal, L v is a draw of N(0, (B + mu I +
+        D)^-1): the route for quasi-random or antithetic z.  Returns out."""
+        return self._apply(self.solver.lib.lbfgsb_hip_qn_shift_sqrt, v, out)
+
+    def sample(self, k: int, seed: int, first: int = 0, mean=None, scale: float = 1.0, log_prob: bool = False,
+               out=None):
+        """k draws from N(mean, scale^2 (B + mu I + D)^-1) on the free rows as a (k, n) tensor: row j is mean + scale
+        L z_(first + j), z_s the standard normal vector of DeviceSolver.qn_draw -- a function of (seed, the global
+        row, s) alone, whichever rows are pinned and however the rows are sharded.  A pinned row of a draw is its
+        mean (+0 without one).  Returns out; with log_prob (out, logp), logp a numpy (k,) array of the draws'
+        log-densities over the free rows of all ranks (the draws are the same bits either way)."""
+        import torch
+        s = self.solver
+        dt = torch.float32 if s.real == np.float32 else torch.float64
+        if out is None:
+            out = torch.empty((int(k), s.n), dtype=dt, device=torch.device("cuda", s.device))
+        out = s._qn_vec(out, "out")
+        if (out.dim() == 1 and k != 1) or (out.dim() == 2 and out.shape[0] != k):
+            raise ValueError("out must have shape (k, n)")
+        mean = s._qn_center(mean, "mean")
+        ldo = s.n if out.dim() == 1 else out.stride(0)
+        mp = None if mean is None else mean.data_ptr()
+        s.wait_stream()
+        if log_prob:
+            logp = np.zeros(int(k), np.float64)
+            check(s.lib.lbfgsb_hip_qn_shift_draw_logpdf(s.h, int(k), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), mp,
+                                                        float(scale), out.data_ptr(), ldo,
+                                                        logp.ctypes.data_as(C.POINTER(C.c_double))))
+            s._qn_done()
+            return out, logp
+        check(s.lib.lbfgsb_hip_qn_shift_draw(s.h, int(k), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), mp,
+                                             float(scale), out.data_ptr(), ldo))
+        s._qn_done()
+        return out
+
+    def quad(self, v, center=None):
+        """(v_j - center)' (B + mu I + D) (v_j - center) over the free rows of all ranks for v of shape (n,) or (k, n):
+        one pass per 4 vectors, nothing written on the device; what v and center hold on pinned rows is not used.
+        Returns a numpy (k,) array, or a float for a 1-d v."""
+        s = self.solver
+        v = s._qn_vec(v, "v")
+        center = s._qn_center(center, "center")
+        k = 1 if v.dim() == 1 else v.shape[0]
+        ldv = s.n if v.dim() == 1 else v.stride(0)
+        q = np.zeros(k, np.float64)
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_shift_quad(s.h, k, v.data_ptr(), ldv, None if center is None else center.data_ptr(),
+                                             q.ctypes.data_as(C.POINTER(C.c_double))))
+        return float(q[0]) if v.dim() == 1 else q
+
+    def log_prob(self, x, mean=None, scale: float = 1.0):
+        """log N(x_j; mean, scale^2 (B + mu I + D)^-1) over the free rows of all ranks for x of shape (n,) or (k, n);
+        0 when every row is pinned.  Returns a numpy (k,) array, or a float for a 1-d x."""
+        s = self.solver
+        x = s._qn_vec(x, "x")
+        mean = s._qn_center(mean, "mean")
+        k = 1 if x.dim() == 1 else x.shape[0]
+        ldx = s.n if x.dim() == 1 else x.stride(0)
+        lp = np.zeros(k, np.float64)
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_shift_logpdf(s.h, k, x.data_ptr(), ldx, None if mean is None else mean.data_ptr(),
+                                               float(scale), lp.ctypes.data_as(C.POINTER(C.c_double))))
+        return float(lp[0]) if x.dim() == 1 else lp
 
 
 class QnOperator:
