@@ -542,6 +542,33 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  * again"), or the root finds the shifted model not positive definite.  LBFGSB_E_ARG, nothing changed and the shift
  * still in force: NULL ctx / v / x / out / h_q / h_logp, k < 1, first < 0, ld < n_local, scale 0 or not finite.  When,
  * streams, the collective rule and REAL32 are qn_shift_solve's, and the run does not notice the calls.
+ *
+ * Entries at index lists.  After a Laplace fit with 1e8 parameters the first question is the marginal covariance and
+ * the correlations of a few of them.  Every entry of the model depends on the rows of [S, Y] at its two indices alone:
+ *   A[a, b]     = alpha [a == b] + r_a N r_b'           (A = B or H, N the 2col x 2col matrix of qn_diag),
+ *   Sigma[a, b] = w_a [a == b] + w_a w_b r_a K^-1 r_b'  (Sigma = (B + mu I + D)^-1 of the shift in force),
+ * so a block at k indices costs one gather of k 2col reals -- no unit vector, no pass over W.  All indices are GLOBAL,
+ * 0-based int64 rows in HOST arrays, as lbfgsb_hip_kkt_list hands them out (copied to the host).  They are checked on
+ * the host, 0 <= idx < n_global, before anything is launched; lists may be unsorted and may repeat indices.  On several
+ * ranks every rank passes the same list, collectively: a rank contributes the rows it owns and exact zeros elsewhere,
+ * the contributions are added in rank order, so the one stored value survives exactly and host results have the same
+ * bits on every rank.
+ *   qn_rows: h_rows[j + c*ldr] = entry h_idx[j] of logical column c of [S, Y] -- c < col: S in ring order from the
+ *     oldest pair, col <= c < 2col: Y -- widened to double, exactly the stored value.  k <= LBFGSB_QN_IDX_MAXK,
+ *     ldr >= k, any number of stored pairs; with no stored pair nothing is written.
+ *   qn_block: h_a[a + b*lda] = A[h_ia[a], h_ib[b]], mode LBFGSB_QN_B or LBFGSB_QN_H.  h_ib = NULL means ib = ia (kb is
+ *     not read): the upper triangle is computed and the lower copied from it, symmetric bit for bit.  ka, kb <=
+ *     LBFGSB_QN_IDX_MAXK, lda >= ka, any number of stored pairs: the diagonal at a list where qn_diag refuses.
+ *   qn_cols: out + j*ldo receives this rank's n_local rows of column h_idx[j] of A (device memory, the context's real
+ *     kind): what qn_apply gives on the unit vector, which never exists.  k <= 128, ldo >= n_local.  The gather, then
+ *     one pass over W per tile of 16 pairs that writes all k outputs (2col*8 + k*8 B per row and tile in fp64).
+ *   qn_shift_block, qn_shift_cols: the same for Sigma, at most LBFGSB_QN_ROOT_MAXCOL stored pairs as qn_shift_set
+ *     demands.  A pinned row or column is exactly +0.  LBFGSB_E_STATE with no shift in force or after the pairs have
+ *     changed ("call qn_shift_set again"), as qn_shift_solve.
+ * The three host-result entries wait for their data whatever LBFGSB_F_NO_RETURN_SYNC says, as qn_quad; the two that
+ * write device memory follow qn_eigvec.  LBFGSB_E_ARG, nothing changed: a NULL pointer, k < 1, k over the cap, an ld
+ * that is too small, an index outside 0 .. n_global - 1, a mode that is not B or H.  When, REAL32 (W and out fp32,
+ * every sum and host result fp64) and the refusals are qn_apply's, and the run does not notice the calls.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
@@ -580,6 +607,14 @@ int lbfgsb_hip_qn_shift_quad(lbfgsb_hip_ctx *ctx, int64_t k, const void *v, int6
                              double *h_q);
 int lbfgsb_hip_qn_shift_logpdf(lbfgsb_hip_ctx *ctx, int64_t k, const void *x, int64_t ldx, const void *mean,
                                double scale, double *h_logp);
+#define LBFGSB_QN_IDX_MAXK 4096
+int lbfgsb_hip_qn_rows(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_idx, double *h_rows, int64_t ldr);
+int lbfgsb_hip_qn_block(lbfgsb_hip_ctx *ctx, int mode, int64_t ka, const int64_t *h_ia, int64_t kb,
+                        const int64_t *h_ib, double *h_a, int64_t lda);
+int lbfgsb_hip_qn_cols(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int64_t *h_idx, void *out, int64_t ldo);
+int lbfgsb_hip_qn_shift_block(lbfgsb_hip_ctx *ctx, int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib,
+                              double *h_a, int64_t lda);
+int lbfgsb_hip_qn_shift_cols(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_idx, void *out, int64_t ldo);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.

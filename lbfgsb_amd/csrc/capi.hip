@@ -354,6 +354,45 @@ int lbfgsb_hip_qn_shift_logpdf(lbfgsb_hip_ctx *ctx, int64_t k, const void *x, in
   return ctx->qn_shift_logpdf(k, x, ldx, mean, scale, h_logp);
 }
 
+// entries at index lists: the shape of a call is checked here, the indices themselves by the solver (qn_idx.hpp),
+// before anything is launched
+static_assert(LBFGSB_QN_IDX_MAXK == lbk::QN_IDX_MAXK, "the header's cap is the gather's");
+static int qn_block_args(const char *who, lbfgsb_hip_ctx *ctx, int64_t ka, const int64_t *h_ia, int64_t kb,
+                         const int64_t *h_ib, double *h_a, int64_t lda) {
+  if (!ctx || !h_ia || !h_a) return fail(LBFGSB_E_ARG, std::string(who) + ": NULL argument");
+  if (ka < 1 || ka > LBFGSB_QN_IDX_MAXK || (h_ib && (kb < 1 || kb > LBFGSB_QN_IDX_MAXK)) || lda < ka)
+    return fail(LBFGSB_E_ARG, std::string(who) + ": k < 1, k > LBFGSB_QN_IDX_MAXK or lda < ka");
+  return 0;
+}
+int lbfgsb_hip_qn_rows(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_idx, double *h_rows, int64_t ldr) {
+  if (!ctx || !h_idx || !h_rows) return fail(LBFGSB_E_ARG, "qn_rows: NULL argument");
+  if (k < 1 || k > LBFGSB_QN_IDX_MAXK || ldr < k)
+    return fail(LBFGSB_E_ARG, "qn_rows: k < 1, k > LBFGSB_QN_IDX_MAXK or ldr < k");
+  return ctx->qn_rows(k, h_idx, h_rows, ldr);
+}
+int lbfgsb_hip_qn_block(lbfgsb_hip_ctx *ctx, int mode, int64_t ka, const int64_t *h_ia, int64_t kb,
+                        const int64_t *h_ib, double *h_a, int64_t lda) {
+  if (const int rc = qn_block_args("qn_block", ctx, ka, h_ia, kb, h_ib, h_a, lda)) return rc;
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_block: mode");
+  return ctx->qn_block(mode, ka, h_ia, h_ib ? kb : ka, h_ib, h_a, lda);
+}
+int lbfgsb_hip_qn_cols(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int64_t *h_idx, void *out, int64_t ldo) {
+  if (!ctx || !h_idx || !out) return fail(LBFGSB_E_ARG, "qn_cols: NULL argument");
+  if (!qn_mode_ok(mode)) return fail(LBFGSB_E_ARG, "qn_cols: mode");
+  if (k < 1 || k > 128 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_cols: k < 1, k > 128 or ldo < n_local");
+  return ctx->qn_cols(mode, k, h_idx, out, ldo);
+}
+int lbfgsb_hip_qn_shift_block(lbfgsb_hip_ctx *ctx, int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib,
+                              double *h_a, int64_t lda) {
+  if (const int rc = qn_block_args("qn_shift_block", ctx, ka, h_ia, kb, h_ib, h_a, lda)) return rc;
+  return ctx->qn_shift_block(ka, h_ia, h_ib ? kb : ka, h_ib, h_a, lda);
+}
+int lbfgsb_hip_qn_shift_cols(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_idx, void *out, int64_t ldo) {
+  if (!ctx || !h_idx || !out) return fail(LBFGSB_E_ARG, "qn_shift_cols: NULL argument");
+  if (k < 1 || k > 128 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_shift_cols: k < 1, k > 128 or ldo < n_local");
+  return ctx->qn_shift_cols(k, h_idx, out, ldo);
+}
+
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
                    const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,
                    double *h_val) {

@@ -315,6 +315,86 @@ inline int qn_shift_coef(int col, double theta, const double *kf, const double *
   return 0;
 }
 
+// ---- entries at index lists (lbfgsb_hip_qn_block / qn_cols and the shifted twins) ----
+// The gathered rows of [S, Y] lie column by column: r[j + c ldr] is entry idx_j of logical column c (c < col: S, else
+// Y), j < k, as the gather delivers them.
+//
+// c_j = N r_j for every row of a list: cf[i + j d], d = 2col (what the columns pass expands: A e_idx_j = alpha e + W c_j)
+inline void qn_rows_times_n(int col, const double *nm, const double *r, int k, int64_t ldr, double *cf) {
+  const int d = 2 * col;
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i < d; ++i) {
+      double t = 0.0;
+      for (int c = 0; c < d; ++c) t = t + nm[i + (size_t)c * d] * r[j + c * ldr];
+      cf[i + (size_t)j * d] = t;
+    }
+}
+// the gathered rows row by row, rt[c + j d] = r[j + c k]: the dot products of a block then read both operands in order
+inline void qn_rows_transposed(int d, const double *r, int k, double *rt) {
+  for (int c = 0; c < d; ++c)
+    for (int j = 0; j < k; ++j) rt[c + (size_t)j * d] = r[j + (size_t)c * k];
+}
+// a[ja + jb lda] = A[ia_ja, ib_jb] for A = alpha I + [S, Y] N [S, Y]' (N symmetric, 2col x 2col: qn_nmat):
+//   alpha [ia_ja == ib_jb] + sum_i ra_ja,i (N rb_jb)_i,  i ascending (the S part first),
+// with N rb_jb formed once per column, kb (2col)^2 operations.  same: ib is ia (rb, ib are not read); the upper
+// triangle is computed, each sum as the mean of its two orders (r_a'(N r_b) and r_b'(N r_a)), and entry (b, a) is a
+// copy of entry (a, b): symmetric bit for bit, as qn_gram_combine's block, and a repeated index repeats its row.
+inline void qn_entries(int col, double alpha, const double *nm, const double *ra, int ka, const int64_t *ia,
+                       const double *rb, int kb, const int64_t *ib, bool same, double *a, int64_t lda) {
+  const int d = 2 * col;
+  if (same) rb = ra, kb = ka, ib = ia;
+  std::vector<double> cf((size_t)std::max(d, 1) * kb), rt((size_t)std::max(d, 1) * ka);
+  qn_rows_times_n(col, nm, rb, kb, kb, cf.data());
+  qn_rows_transposed(d, ra, ka, rt.data());
+  for (int jb = 0; jb < kb; ++jb)
+    for (int ja = 0; ja < (same ? jb + 1 : ka); ++ja) {
+      double t = dot_seq(d, &rt[(size_t)ja * d], &cf[(size_t)jb * d]);
+      if (same)  // (both orders: a repeated index then gives a repeated row and column bit for bit)
+        t = 0.5 * (t + dot_seq(d, &rt[(size_t)jb * d], &cf[(size_t)ja * d]));
+      const double v = (ia[ja] == ib[jb] ? alpha : 0.0) + t;
+      a[ja + jb * lda] = v;
+      if (same) a[jb + ja * lda] = v;
+    }
+}
+// c_j = K^-1 (w_j r_j) in the [S, Y] basis for every row of a list, by qn_shift_coef on qn_shift_factor's kf:
+// cf[i + j d] (what the shifted columns pass expands: Sigma e_idx_j = w_j e + w o (W c_j)).  Returns 0 or
+// qn_shift_coef's info.
+inline int qn_shift_rows_coef(int col, double theta, const double *kf, const double *r, const double *w, int k,
+                              int64_t ldr, double *cf) {
+  const int d = 2 * col;
+  std::vector<double> t((size_t)std::max(d, 1));
+  for (int j = 0; j < k; ++j) {
+    for (int c = 0; c < d; ++c) t[(size_t)c] = w[j] * r[j + c * ldr];
+    const int info = qn_shift_coef(col, theta, kf, t.data(), t.data() + col, cf + (size_t)j * d, cf + (size_t)j * d + col);
+    if (info) return info;
+  }
+  return 0;
+}
+// The twin for Sigma = (B + mu I + D)^-1 = diag(w) + diag(w) W K^-1 W' diag(w): wa, wb are the weights at the indices
+// (0 on a pinned row),
+//   a[ja + jb lda] = wa_ja [ia_ja == ib_jb] + wa_ja sum_i ra_ja,i (K^-1 (wb_jb rb_jb))_i,
+// and exactly +0 where either row is pinned.  Returns 0 or qn_shift_coef's info, a then as it was.
+inline int qn_shift_entries(int col, double theta, const double *kf, const double *ra, const double *wa, int ka,
+                            const int64_t *ia, const double *rb, const double *wb, int kb, const int64_t *ib,
+                            bool same, double *a, int64_t lda) {
+  const int d = 2 * col;
+  if (same) rb = ra, wb = wa, kb = ka, ib = ia;
+  std::vector<double> cf((size_t)std::max(d, 1) * kb);
+  const int info = qn_shift_rows_coef(col, theta, kf, rb, wb, kb, kb, cf.data());
+  if (info) return info;
+  std::vector<double> rt((size_t)std::max(d, 1) * ka);
+  qn_rows_transposed(d, ra, ka, rt.data());
+  for (int jb = 0; jb < kb; ++jb)
+    for (int ja = 0; ja < (same ? jb + 1 : ka); ++ja) {
+      double t = wa[ja] * dot_seq(d, &rt[(size_t)ja * d], &cf[(size_t)jb * d]);
+      if (same) t = 0.5 * (t + wa[jb] * dot_seq(d, &rt[(size_t)jb * d], &cf[(size_t)ja * d]));
+      const double v = wa[ja] == 0.0 || wb[jb] == 0.0 ? 0.0 : (ia[ja] == ib[jb] ? wa[ja] : 0.0) + t;
+      a[ja + jb * lda] = v;
+      if (same) a[jb + ja * lda] = v;
+    }
+  return 0;
+}
+
 // ---- the square root and the log-determinant of the model (lbfgsb_hip_qn_apply's root modes, qn_logdet, qn_draw) ----
 // Both models are A = alpha I + W N W' with W = [S, Y] and G = W'W.  With P = G^(1/2) and P N P = V diag(delta) V'
 // (delta: the non-zero eigenvalues of W N W'),

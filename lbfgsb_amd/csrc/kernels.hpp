@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "qn_idx.hpp"      // QN_IDX_MAXK, QN_IDX_BUF: index lists of the curvature-model operators and their chunks
 #include "qn_plan.hpp"     // QN_TILE, QN_KMAX, qn_mc, qn_kmax, QnCarry: the tiling of the curvature-model operators
 #include "res_layout.hpp"  // the slot layouts of the results, MAXM, maxc_for, RES_MAX, the split pass's sizes
 
@@ -614,6 +615,22 @@ hipError_t launch_qn_shift_wtd(const Queue &q, int64_t n, WStore<T> w, int head,
 template <typename T>
 hipError_t launch_qn_basis(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, bool acc,
                            const double *coef, int k, T *out, int64_t ldo);
+
+// Entries at index lists (k_qn_idx.hip, lbfgsb_hip_qn_rows / qn_block / qn_cols and the shifted twins).
+// The gather: out[j + c kc] = entry idx[j] of logical column c of [S, Y] (c < col: S, else Y), widened to double, and
+// with wgt != NULL one more column out[j + 2 col kc] = wgt[idx[j] - row0]; 0.0 for a row outside row0 .. row0 + n - 1.
+// idx: DEVICE memory, kc global rows that the host has checked; kc (2 col [+ 1]) <= QN_IDX_BUF doubles of out, a buffer
+// of the caller's own.  w.lmask may be set: the layout is read as it is.
+template <typename T>
+hipError_t launch_qn_rows(const Queue &q, int64_t n, int64_t row0, WStore<T> w, int head, int col,
+                          const int64_t *idx, int kc, const double *wgt, double *out);
+// launch_qn_basis with the row weight and the diagonal term fused: out_j[i] (+)= f_i ([S, Y](i, tile) coef[j * 2 mc
+// ...]) for all j < k, f_i = wgt[i] (wgt == NULL: 1; a row with wgt = 0 stores +0), and the first tile (acc = false)
+// adds dterm[j] on the row idx[j] - row0 where this rank owns it.  coef, dterm, idx: DEVICE memory.
+template <typename T>
+hipError_t launch_qn_cols(const Queue &q, int64_t n, int64_t row0, WStore<T> w, int head, int col, int c0, int mc,
+                          bool acc, const double *coef, const double *dterm, const int64_t *idx, const double *wgt,
+                          int k, T *out, int64_t ldo);
 
 // Draws of the model (k_qn_draw.hip): the two passes above with the vectors generated, never loaded -- z_k[i] is the
 // N(0, 1) deviate of (seed, row0 + i, s0 + k) (philox.hpp).  k = 1, 2 or 4 (qn_kmax) samples from s0; s0 even

@@ -1873,6 +1873,7 @@ class Solver final : public lbfgsb_hip_ctx {
 #include "solver_state.inl"     // state exchange, per-kernel doors, communicators
 #include "solver_doors.inl"     // routine doors (active, errclb, cauchy, freev, formk, cmprlb, subsm, lnsrlb, matupd)
 #include "solver_qn.inl"        // the curvature model B, H = B^-1 as device operators (qn_apply, qn_diag)
+#include "solver_qn_idx.inl"    // its entries, sub-blocks and columns at index lists (qn_rows, qn_block, qn_cols)
 #include "solver_kkt.inl"       // the active set, the multipliers and the projected gradient (kkt, kkt_list)
 };
 

@@ -180,6 +180,15 @@ struct lbfgsb_hip_ctx {
   virtual int qn_shift_quad(int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) = 0;
   virtual int qn_shift_logpdf(int64_t k, const void *x, int64_t ldx, const void *mean, double scale,
                               double *h_logp) = 0;
+  // entries, sub-blocks and columns at index lists (solver_qn_idx.inl, lbfgsb_hip_qn_rows / qn_block / qn_cols);
+  // h_ib may be NULL: ib = ia
+  virtual int qn_rows(int64_t k, const int64_t *h_idx, double *h_rows, int64_t ldr) = 0;
+  virtual int qn_block(int mode, int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib, double *h_a,
+                       int64_t lda) = 0;
+  virtual int qn_cols(int mode, int64_t k, const int64_t *h_idx, void *out, int64_t ldo) = 0;
+  virtual int qn_shift_block(int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib, double *h_a,
+                             int64_t lda) = 0;
+  virtual int qn_shift_cols(int64_t k, const int64_t *h_idx, void *out, int64_t ldo) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

@@ -53,6 +53,9 @@
       public :: lbfgsb_qn_shift_set, lbfgsb_qn_shift_solve, lbfgsb_qn_shift_logdet, lbfgsb_qn_shift_diag
       public :: lbfgsb_qn_shift_sqrt, lbfgsb_qn_shift_draw, lbfgsb_qn_shift_draw_logpdf   ! its factor and draws
       public :: lbfgsb_qn_shift_quad, lbfgsb_qn_shift_logpdf                              ! ... and densities
+      public :: lbfgsb_qn_rows, lbfgsb_qn_block, lbfgsb_qn_cols       ! entries of B, H at lists of global 0-based rows
+      public :: lbfgsb_qn_shift_block, lbfgsb_qn_shift_cols           ! ... and of (B + mu I + diag(d))^-1
+      integer,parameter,public :: LBFGSB_QN_IDX_MAXK = 4096
                                                        ! solves, log det and diagonal of (B + mu I + diag(d))^-1
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
                                                        ! gradient of device arrays (lbfgsb_hip_kkt / _kkt_list)
@@ -297,6 +300,46 @@
             real(c_double) :: logp(*)
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_draw_logpdf
+         function lbfgsb_hip_qn_rows(ctx,k,idx,rows,ldr) bind(C,name='lbfgsb_hip_qn_rows') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx
+            integer(c_int64_t),value :: k, ldr
+            integer(c_int64_t) :: idx(*)
+            real(c_double) :: rows(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_rows
+         function lbfgsb_hip_qn_block(ctx,mode,ka,ia,kb,ib,a,lda) bind(C,name='lbfgsb_hip_qn_block') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, ib
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: ka, kb, lda
+            integer(c_int64_t) :: ia(*)
+            real(c_double) :: a(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_block
+         function lbfgsb_hip_qn_cols(ctx,mode,k,idx,out,ldo) bind(C,name='lbfgsb_hip_qn_cols') result(rc)
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, out
+            integer(c_int),value :: mode
+            integer(c_int64_t),value :: k, ldo
+            integer(c_int64_t) :: idx(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_cols
+         function lbfgsb_hip_qn_shift_block(ctx,ka,ia,kb,ib,a,lda) bind(C,name='lbfgsb_hip_qn_shift_block') result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, ib
+            integer(c_int64_t),value :: ka, kb, lda
+            integer(c_int64_t) :: ia(*)
+            real(c_double) :: a(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_block
+         function lbfgsb_hip_qn_shift_cols(ctx,k,idx,out,ldo) bind(C,name='lbfgsb_hip_qn_shift_cols') result(rc)
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, out
+            integer(c_int64_t),value :: k, ldo
+            integer(c_int64_t) :: idx(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_shift_cols
          function lbfgsb_hip_kkt(ctx,x,l,u,nbd,g,tol,pg,mult,status,cnt,val) bind(C,name='lbfgsb_hip_kkt') result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
             type(c_ptr),value :: ctx, x, l, u, nbd, g, pg, mult, status
@@ -757,6 +800,66 @@
       rc = lbfgsb_hip_qn_draw_logpdf(ctx, int(mode, c_int), int(k, c_int64_t), seed, int(first, c_int64_t), mean, &
                                      scale, out, int(ldo, c_int64_t), logp)
       end subroutine lbfgsb_qn_draw_logpdf
+
+      ! Entries at index lists (include/lbfgsb_hip.h, "Entries at index lists").  idx, ia, ib are HOST arrays of GLOBAL
+      ! 0-BASED int64 rows, as lbfgsb_kkt_list produces them (copied to the host); lists may be unsorted and repeat.
+      ! lbfgsb_qn_rows: rows(j + (c - 1) ldr), j = 1 .. k, is entry idx(j) of logical column c of [S, Y] (c <= col: S,
+      ! oldest pair first, then Y); k <= LBFGSB_QN_IDX_MAXK.  lbfgsb_qn_block: a(i + (j - 1) lda) = A(ia(i), ib(j)), A = B
+      ! or H by mode; kb = 0 means ib = ia (ib is not read): the block is then symmetric bit for bit -- with
+      ! LBFGSB_QN_H the marginal covariance of those parameters.  lbfgsb_qn_cols: column idx(j) of A at out + (j - 1)
+      ! ldo (device memory, n reals each), k <= 128.  lbfgsb_qn_shift_block / _cols: the same for (B + mu I + diag(d))^-1
+      ! of the shift in force (lbfgsb_qn_shift_set); pinned rows and columns are exactly +0.
+      subroutine lbfgsb_qn_rows(ctx, k, idx, rows, ldr, rc)
+      type(c_ptr),intent(in) :: ctx
+      integer,intent(in) :: k, ldr
+      integer(c_int64_t),intent(in) :: idx(*)
+      real(c_double),intent(inout) :: rows(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_rows(ctx, int(k, c_int64_t), idx, rows, int(ldr, c_int64_t))
+      end subroutine lbfgsb_qn_rows
+
+      subroutine lbfgsb_qn_block(ctx, mode, ka, ia, kb, ib, a, lda, rc)
+      type(c_ptr),intent(in) :: ctx
+      integer,intent(in) :: mode, ka, kb, lda
+      integer(c_int64_t),intent(in) :: ia(*)
+      integer(c_int64_t),intent(in),target :: ib(*)
+      real(c_double),intent(inout) :: a(*)
+      integer,intent(out) :: rc
+      type(c_ptr) :: pb
+      pb = c_null_ptr
+      if (kb > 0) pb = c_loc(ib)
+      rc = lbfgsb_hip_qn_block(ctx, int(mode, c_int), int(ka, c_int64_t), ia, int(kb, c_int64_t), pb, a, &
+                               int(lda, c_int64_t))
+      end subroutine lbfgsb_qn_block
+
+      subroutine lbfgsb_qn_cols(ctx, mode, k, idx, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, out
+      integer,intent(in) :: mode, k, ldo
+      integer(c_int64_t),intent(in) :: idx(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_cols(ctx, int(mode, c_int), int(k, c_int64_t), idx, out, int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_cols
+
+      subroutine lbfgsb_qn_shift_block(ctx, ka, ia, kb, ib, a, lda, rc)
+      type(c_ptr),intent(in) :: ctx
+      integer,intent(in) :: ka, kb, lda
+      integer(c_int64_t),intent(in) :: ia(*)
+      integer(c_int64_t),intent(in),target :: ib(*)
+      real(c_double),intent(inout) :: a(*)
+      integer,intent(out) :: rc
+      type(c_ptr) :: pb
+      pb = c_null_ptr
+      if (kb > 0) pb = c_loc(ib)
+      rc = lbfgsb_hip_qn_shift_block(ctx, int(ka, c_int64_t), ia, int(kb, c_int64_t), pb, a, int(lda, c_int64_t))
+      end subroutine lbfgsb_qn_shift_block
+
+      subroutine lbfgsb_qn_shift_cols(ctx, k, idx, out, ldo, rc)
+      type(c_ptr),intent(in) :: ctx, out
+      integer,intent(in) :: k, ldo
+      integer(c_int64_t),intent(in) :: idx(*)
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_shift_cols(ctx, int(k, c_int64_t), idx, out, int(ldo, c_int64_t))
+      end subroutine lbfgsb_qn_shift_cols
 
       ! The active set, the multipliers and the projected gradient (include/lbfgsb_hip.h, "The active set, the bound
       ! multipliers and the projected gradient as device data"): one pass over the device arrays x, l, u, nbd, g of

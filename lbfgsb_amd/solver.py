@@ -509,6 +509,74 @@ class DeviceSolver:
         self._qn_done()
         return out
 
+    # ---- entries at index lists (include/lbfgsb_hip.h "Entries at index lists") ----
+    @staticmethod
+    def _qn_idx(idx, what="idx"):
+        """an index list as a contiguous host int64 array: numpy arrays, sequences or torch tensors (a device tensor,
+        such as kkt_indices returns, is copied to the host)"""
+        if hasattr(idx, "detach") and hasattr(idx, "cpu"):
+            idx = idx.detach().cpu().numpy()
+        a = np.asarray(idx)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("%s must hold integers" % what)
+        a = np.ascontiguousarray(a, np.int64).reshape(-1)
+        if a.size < 1:
+            raise ValueError("%s is empty" % what)
+        return a
+
+    def qn_rows(self, idx):
+        """The rows of the stored pairs at the global 0-based indices idx as a numpy (k, 2 col) float64 array: entry
+        [j, c] is row idx[j] of S (c < col, oldest pair first) or of Y (c >= col), exactly the stored value.  One
+        gather, no pass over W; k <= capi.QN_IDX_MAXK.  Collective on sharded contexts: every rank passes the same
+        list and receives the same array."""
+        idx = self._qn_idx(idx)
+        k = int(idx.size)
+        buf = np.full((2 * self.m, k), np.nan, np.float64)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_rows(self.h, k, idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          buf.ctypes.data_as(C.POINTER(C.c_double)), k))
+        written = int(np.count_nonzero(~np.isnan(buf).all(axis=1)))  # (2 col columns were written, no others)
+        return np.ascontiguousarray(buf[:written].T)
+
+    def qn_block(self, ia, ib=None, inverse: bool = False):
+        """A[ia, ib] for A = B (inverse=False) or H as a numpy (ka, kb) float64 array, from the rows of the pairs at
+        the global 0-based indices alone: alpha [ia_a == ib_b] + r_a N r_b'.  ib=None: ib = ia, symmetric bit for
+        bit -- with inverse=True the marginal covariance of these parameters under the Laplace posterior N(x*, H).
+        Lists may be unsorted and repeat indices; at most capi.QN_IDX_MAXK each, any number of stored pairs.
+        Collective on sharded contexts (the same list, the same bits on every rank)."""
+        ia = self._qn_idx(ia, "ia")
+        ib = None if ib is None else self._qn_idx(ib, "ib")
+        ka, kb = int(ia.size), int(ia.size if ib is None else ib.size)
+        a = np.zeros((kb, ka), np.float64)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_block(self.h, capi.QN_H if inverse else capi.QN_B, ka,
+                                           ia.ctypes.data_as(C.POINTER(C.c_int64)), kb,
+                                           None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           a.ctypes.data_as(C.POINTER(C.c_double)), ka))
+        return np.ascontiguousarray(a.T)
+
+    def _qn_cols_out(self, k, out):
+        import torch
+        dt = torch.float32 if self.real == np.float32 else torch.float64
+        if out is None:
+            out = torch.empty((k, self.n), dtype=dt, device=torch.device("cuda", self.device))
+        out = self._qn_vec(out, "out")
+        if (out.dim() == 1 and k != 1) or (out.dim() == 2 and out.shape[0] != k):
+            raise ValueError("out must have shape (k, n)")
+        return out, (self.n if out.dim() == 1 else out.stride(0))
+
+    def qn_cols(self, idx, out=None, inverse: bool = False):
+        """The columns A[:, idx[j]] of B (inverse=False) or H as a (k, n) tensor of this rank's rows, k <= 128: what
+        qn_apply gives on unit vectors, without the unit vectors -- the gather of k rows, then one pass over the
+        pairs per 16 of them that writes all k columns.  Returns out."""
+        idx = self._qn_idx(idx)
+        out, ldo = self._qn_cols_out(int(idx.size), out)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_cols(self.h, capi.QN_H if inverse else capi.QN_B, int(idx.size),
+                                          idx.ctypes.data_as(C.POINTER(C.c_int64)), out.data_ptr(), ldo))
+        self._qn_done()
+        return out
+
     def qn_shift(self, d=None, mu: float = 0.0) -> "QnShifted":
         """The model plus a diagonal, B + mu I + diag(d), as a QnShifted with .solve(v), .logdet(), .diag(), .pinned,
         and .sqrt(v), .sample(k, seed), .quad(v), .log_prob(x) of N(mean, scale^2 (B + mu I + diag(d))^-1).  d: an (n,) tensor of this rank's rows or None (D = 0); an entry +inf pins its row -- the row drops
@@ -889,6 +957,34 @@ class QnShifted:
         s._qn_done()
         return out
 
+    def block(self, ia, ib=None):
+        """Sigma[ia, ib] of Sigma = (B + mu I + D)^-1 as a numpy (ka, kb) float64 array at global 0-based indices
+        (ib=None: ib = ia, symmetric bit for bit): the marginal covariance of these parameters with the pinned rows
+        held fixed.  A pinned row or column is exactly +0.  One gather of the rows and weights, no pass over W.
+        With kkt_indices: block(solver.kkt_indices(report.status, 0)[:64]) on a shift with d = inf at the bounds."""
+        s = self.solver
+        ia = s._qn_idx(ia, "ia")
+        ib = None if ib is None else s._qn_idx(ib, "ib")
+        ka, kb = int(ia.size), int(ia.size if ib is None else ib.size)
+        a = np.zeros((kb, ka), np.float64)
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_shift_block(s.h, ka, ia.ctypes.data_as(C.POINTER(C.c_int64)), kb,
+                                              None if ib is None else ib.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              a.ctypes.data_as(C.POINTER(C.c_double)), ka))
+        return np.ascontiguousarray(a.T)
+
+    def columns(self, idx, out=None):
+        """The columns Sigma[:, idx[j]] as a (k, n) tensor of this rank's rows, k <= 128; pinned rows are +0 and a
+        pinned idx[j] gives a row of +0.  Returns out."""
+        s = self.solver
+        idx = s._qn_idx(idx)
+        out, ldo = s._qn_cols_out(int(idx.size), out)
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_shift_cols(s.h, int(idx.size), idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             out.data_ptr(), ldo))
+        s._qn_done()
+        return out
+
     def _apply(self, entry, v, out):
         s = self.solver
         v = s._qn_vec(v, "v")
@@ -1033,6 +1129,22 @@ class QnOperator:
         if self.root:
             raise ValueError("gram() takes B or H, not a square root")
         return self.solver.qn_gram(v, center=center, inverse=self.inverse)
+
+    def block(self, ia, ib=None):
+        """A[ia, ib] at global 0-based index lists as a numpy (ka, kb) array (DeviceSolver.qn_block)"""
+        if self.root:
+            raise ValueError("block() takes B or H, not a square root")
+        return self.solver.qn_block(ia, ib, inverse=self.inverse)
+
+    def columns(self, idx, out=None):
+        """the columns A[:, idx[j]] as a (k, n) tensor of this rank's rows (DeviceSolver.qn_cols)"""
+        if self.root:
+            raise ValueError("columns() takes B or H, not a square root")
+        return self.solver.qn_cols(idx, out=out, inverse=self.inverse)
+
+    def marginal(self, idx):
+        """the block of this operator at idx: with inverse=True the marginal covariance of those parameters"""
+        return self.block(idx)
 
     def _spectrum(self, what):
         if self.root:
