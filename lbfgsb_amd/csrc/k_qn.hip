@@ -26,9 +26,7 @@ namespace lbk {
 // (at K = 1 that is DD itself: launch_qn_wtv hands it to qn_wtd_kernel).
 // The plain pass (qn_wtv_kernel) is the body with all three off.
 template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT, bool CEN, bool DD, bool GG = false>
-__device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                            const T *__restrict__ zero, int64_t ldw, int m, int head, int col, int c0,
-                                            const uint64_t *__restrict__ lmask, const QnVecs<T> &v,
+__device__ __forceinline__ void qn_wtv_body(int64_t n, QN_TILE_PARAMS(T), const QnVecs<T> &v,
                                             const T *__restrict__ center, double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
   static_assert(!VSLOT || !(CEN || DD || GG), "a center and the squared norm belong to vectors in natural order");
@@ -45,6 +43,8 @@ __device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws,
     for (int kk = 0; kk < K; ++kk) ldx<W, NT>(v.p[kk] + (VSLOT ? s : i), vv[kk]);
     double cc[CEN ? W : 1];
     if constexpr (CEN) ldx<W, NT>(center + i, cc);
+    // (the tile's loads stay written out here, on the flat arguments, instead of qn_ld_tile on a view: through the
+    //  helper qn_wtd_kernel<float, 5, 1, 2> and <float, 5, 2, 2> took 16 and 12 registers more and lost a wave per SIMD)
 #pragma unroll
     for (int j = 0; j < MC; ++j) {
       const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
@@ -62,13 +62,7 @@ __device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws,
     }
 #pragma unroll
     for (int kk = 0; kk < K; ++kk)
-#pragma unroll
-      for (int j = 0; j < MC; ++j)
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[kk * 2 * MC + j] += a[j][w] * vv[kk][w];
-          acc[kk * 2 * MC + MC + j] += b[j][w] * vv[kk][w];
-        }
+      qn_dot_acc<MC, W>(acc + kk * 2 * MC, a, b, vv[kk]);
     if constexpr (DD) {
 #pragma unroll
       for (int kk = 0; kk < K; ++kk)
@@ -89,31 +83,23 @@ __device__ __forceinline__ void qn_wtv_body(int64_t n, const T *__restrict__ ws,
 }
 
 template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_wtv_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                       int col, int c0, const uint64_t *__restrict__ lmask,
-                                                       QnVecs<T> v, double *part) {
-  qn_wtv_body<T, MC, K, V, CW, VSLOT, NT, false, false>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, nullptr,
-                                                        part);
+__global__ __launch_bounds__(BLOCK) void qn_wtv_kernel(int64_t n, QN_TILE_PARAMS(T), QnVecs<T> v,
+                                                       double *part) {
+  qn_wtv_body<T, MC, K, V, CW, VSLOT, NT, false, false>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, nullptr, part);
 }
 
 // the W'V pass of a quadratic form (lbfgsb_hip_qn_quad / qn_logpdf): the vectors centred, d'd on the first tile
 template <typename T, int MC, int K, int V, bool CW, bool NT, bool CEN, bool DD>
-__global__ __launch_bounds__(BLOCK) void qn_wtd_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                       int col, int c0, const uint64_t *__restrict__ lmask,
-                                                       QnVecs<T> v, const T *__restrict__ center, double *part) {
+__global__ __launch_bounds__(BLOCK) void qn_wtd_kernel(int64_t n, QN_TILE_PARAMS(T), QnVecs<T> v,
+                                                       const T *__restrict__ center, double *part) {
   qn_wtv_body<T, MC, K, V, CW, false, NT, CEN, DD>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, center, part);
 }
 
 // the W'V pass of a Gram matrix (lbfgsb_hip_qn_gram): the first tile's launch, the block's d_a'd_b along (K >= 2)
 template <typename T, int MC, int K, int V, bool CW, bool NT, bool CEN>
-__global__ __launch_bounds__(BLOCK) void qn_wtg_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                       int col, int c0, const uint64_t *__restrict__ lmask,
-                                                       QnVecs<T> v, const T *__restrict__ center, double *part) {
-  qn_wtv_body<T, MC, K, V, CW, false, NT, CEN, false, true>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, center,
-                                                            part);
+__global__ __launch_bounds__(BLOCK) void qn_wtg_kernel(int64_t n, QN_TILE_PARAMS(T), QnVecs<T> v,
+                                                       const T *__restrict__ center, double *part) {
+  qn_wtv_body<T, MC, K, V, CW, false, NT, CEN, false, true>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, v, center, part);
 }
 
 // sums: slot ia * KB + ib = d_ia'd_ib, d_ia = a_ia - center of one block of vectors, d_ib = b_ib - center of another:
@@ -172,10 +158,7 @@ __global__ __launch_bounds__(BLOCK) void qn_finalize_kernel(const double *__rest
 
 // out_kk[i] = alpha src_kk[i] + sum_j cf.c[kk][j] S(i, c0 + j) + cf.c[kk][MC + j] Y(i, c0 + j)
 template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_expand_kernel(int64_t n, const T *__restrict__ ws,
-                                                          const T *__restrict__ wy, const T *__restrict__ zero,
-                                                          int64_t ldw, int m, int head, int col, int c0,
-                                                          const uint64_t *__restrict__ lmask, QnCoef<MC, K> cf,
+__global__ __launch_bounds__(BLOCK) void qn_expand_kernel(int64_t n, QN_TILE_PARAMS(T), QnCoef<MC, K> cf,
                                                           QnVecs<T> src, QnOuts<T> out) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
   for_rows<T, V>(n, [&](int64_t i, auto wt) {
@@ -184,6 +167,8 @@ __global__ __launch_bounds__(BLOCK) void qn_expand_kernel(int64_t n, const T *__
     double x[K][W], a[MC][W], b[MC][W];
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) ldx<W, false>(src.p[kk] + i, x[kk]);
+    // (loads and sum written out, not qn_ld_tile and qn_comb: with the helpers qn_expand_kernel<float, 16, 1, 1> went
+    //  from 130 to 169 registers, 3 waves per SIMD to 2)
 #pragma unroll
     for (int j = 0; j < MC; ++j) {
       const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
@@ -220,28 +205,15 @@ __global__ __launch_bounds__(BLOCK) void qn_diag_kernel(int64_t n, const T *__re
   __shared__ double sn[NP];
   for (int e = threadIdx.x; e < NP; e += BLOCK) sn[e] = np[e];
   __syncthreads();
+  const QnTile<T> t{ws, wy, zero, ldw, m, head, col, 0, lmask};
   for_rows<T, 1>(n, [&](int64_t i, auto) {
     // (N is re-read from LDS for every row: hoisted out of the row loop, its 2080 entries at 32 pairs would live
     //  in registers and spill to scratch -- the memory clobber keeps the reads here)
     asm volatile("" ::: "memory");
     const int64_t s = qn_slot<CW>(lmask, i);
     double r[D][1];
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(j, col, head, m, ldw) + s;
-      ld_col<T, 1, NT>(j < col, ws + off, zero, r[j]);
-      ld_col<T, 1, NT>(j < col, wy + off, zero, r[MC + j]);
-    }
-    double acc = 0.0;
-    int e = 0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      double t = 0.0;
-#pragma unroll
-      for (int b = a; b < D; ++b) t += sn[e++] * r[b][0];
-      acc += r[a][0] * t;
-    }
-    const double o[1] = {alpha + acc};
+    qn_ld_tile<T, MC, 1, NT>(t, s, r, r + MC);
+    const double o[1] = {alpha + qn_rnr<MC>(sn, r)};
     stnt<1>(out + i, o);
   });
 }
@@ -265,14 +237,13 @@ hipError_t launch_qn_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int c
   //  the K squared norms and the center's V entries add 2 (K + V) <= 8 registers to the plain pass's operands and sums
   //  -- 140 against 136 at the largest, mc = 10, k = 1: three waves per SIMD still; a Gram has them at 5 columns and
   //  K = 2 only)
-  bool vec2 = !vslot && 2 * mc * k <= 20 && (!center || aligned_for(center, 2));
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
+  const bool vec2 = !vslot && 2 * mc * k <= 20 && (!center || aligned_for(center, 2)) && all_aligned_for(v.p, k, 2);
   int g = 0;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
     auto go = [&](auto kern, auto... cen) {
       g = grid_for_w(q, n, V, (const void *)kern);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                         w.lmask, v, cen..., part);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), v, cen...,
+                         part);
     };
     if (!center && carry == QnCarry::None) {  // (the later column tiles of an uncentred form too: the plain pass)
       QN_DISPATCH_BOOL(vslot, VS, go(qn_wtv_kernel<T, MC, K, V, CW, VS, NT>));
@@ -306,9 +277,7 @@ template <typename T>
 hipError_t launch_qn_dtd(const Queue &q, int64_t n, QnVecs<T> a, int ka, QnVecs<T> b, int kb, const T *center,
                          double *part, double *res) {
   if ((ka != 1 && ka != 2 && ka != 4) || (kb != 1 && kb != 2 && kb != 4)) return hipErrorInvalidValue;
-  bool vec2 = !center || aligned_for(center, 2);
-  for (int kk = 0; kk < ka; ++kk) vec2 = vec2 && aligned_for(a.p[kk], 2);
-  for (int kk = 0; kk < kb; ++kk) vec2 = vec2 && aligned_for(b.p[kk], 2);
+  const bool vec2 = (!center || aligned_for(center, 2)) && all_aligned_for(a.p, ka, 2) && all_aligned_for(b.p, kb, 2);
   int g = 0;
   QN_DISPATCH_KAB(ka, KA, QN_DISPATCH_KAB(kb, KB, QN_DISPATCH_BOOL(vec2, V2, QN_DISPATCH_BOOL(q.nt, NT,
       QN_DISPATCH_BOOL(center != nullptr, CEN, {
@@ -324,15 +293,13 @@ template <typename T>
 hipError_t launch_qn_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                             const double *coef, double alpha, QnVecs<T> src, QnOuts<T> out) {
   if (!qn_block_ok(mc, k)) return hipErrorInvalidValue;
-  bool vec2 = 2 * mc * k <= 20;
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(src.p[kk], 2) && aligned_for((const T *)out.p[kk], 2);
+  const bool vec2 = 2 * mc * k <= 20 && all_aligned_for(src.p, k, 2) && all_aligned_for(out.p, k, 2);
   bool done = false;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
     const QnCoef<MC, K> cf = qn_coef_args<MC, K>(coef, alpha);
     auto kern = qn_expand_kernel<T, MC, K, V, CW, NT>;
     const int g = grid_for_w(q, n, V, (const void *)kern);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, cf, src, out);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), cf, src, out);
     done = true;
   }))));
   if (!done) return hipErrorInvalidValue;

@@ -23,10 +23,8 @@ namespace lbk {
 // and 2MC K and 2MC K + K are on the same side of its scatter threshold for every MC, K here), on the same grid
 // (launch_qn_wtz sizes it from the plain kernel for both).
 template <typename T, int MC, int K, int V, bool CW, bool NT, bool ZZ>
-__device__ __forceinline__ void qn_wtz_body(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                            const T *__restrict__ zero, int64_t ldw, int m, int head, int col, int c0,
-                                            const uint64_t *__restrict__ lmask, uint64_t seed, int64_t row0,
-                                            int64_t s0, double *part) {
+__device__ __forceinline__ void qn_wtz_body(int64_t n, const QnTile<T> &t, uint64_t seed, int64_t row0, int64_t s0,
+                                            double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
   constexpr int NW = 2 * MC * K, NACC = NW + (ZZ ? K : 0);
   static_assert((NW >= 16) == (NACC >= 16), "block_reduce_store reduces the W'z slots as the plain pass does");
@@ -35,25 +33,15 @@ __device__ __forceinline__ void qn_wtz_body(int64_t n, const T *__restrict__ ws,
   for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
   for_rows<T, V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
-    const int64_t s = qn_slot<CW>(lmask, i);
+    const int64_t s = qn_slot<CW>(t.lmask, i);
     double a[MC][W], b[MC][W];
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
-      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
-    }
+    qn_ld_tile<T, MC, W, NT>(t, s, a, b);
 #pragma unroll
     for (int w = 0; w < W; ++w) {
       double z[K];
       qn_gauss<K>(seed, (uint64_t)(row0 + i + w), (uint64_t)s0, z);
 #pragma unroll
-      for (int kk = 0; kk < K; ++kk)
-#pragma unroll
-        for (int j = 0; j < MC; ++j) {
-          acc[kk * 2 * MC + j] += a[j][w] * z[kk];
-          acc[kk * 2 * MC + MC + j] += b[j][w] * z[kk];
-        }
+      for (int kk = 0; kk < K; ++kk) qn_dot_acc<MC, W>(acc + kk * 2 * MC, a, b, w, z[kk]);
       if constexpr (ZZ) {
 #pragma unroll
         for (int kk = 0; kk < K; ++kk) acc[NW + kk] += z[kk] * z[kk];
@@ -64,41 +52,30 @@ __device__ __forceinline__ void qn_wtz_body(int64_t n, const T *__restrict__ ws,
 }
 
 template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_wtz_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                       const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                       int col, int c0, const uint64_t *__restrict__ lmask,
-                                                       uint64_t seed, int64_t row0, int64_t s0, double *part) {
-  qn_wtz_body<T, MC, K, V, CW, NT, false>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, seed, row0, s0, part);
+__global__ __launch_bounds__(BLOCK) void qn_wtz_kernel(int64_t n, QN_TILE_PARAMS(T), uint64_t seed,
+                                                       int64_t row0, int64_t s0, double *part) {
+  qn_wtz_body<T, MC, K, V, CW, NT, false>(n, QN_TILE_VIEW(T), seed, row0, s0, part);
 }
 
 template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_wtzz_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                        const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                        int col, int c0, const uint64_t *__restrict__ lmask,
-                                                        uint64_t seed, int64_t row0, int64_t s0, double *part) {
-  qn_wtz_body<T, MC, K, V, CW, NT, true>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, seed, row0, s0, part);
+__global__ __launch_bounds__(BLOCK) void qn_wtzz_kernel(int64_t n, QN_TILE_PARAMS(T), uint64_t seed,
+                                                        int64_t row0, int64_t s0, double *part) {
+  qn_wtz_body<T, MC, K, V, CW, NT, true>(n, QN_TILE_VIEW(T), seed, row0, s0, part);
 }
 
 // first (tile c0 = 0): out_kk[i] =mean[i] + cf.alpha z_kk[i] + sum_j cf.c[kk][j] S(i, j) + cf.c[kk][MC + j] Y(i, j)
 // with mean[i] = 0 for a NULL mean; later tiles: out_kk[i] += sum_j ... over the columns c0 + j
 template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_draw_kernel(int64_t n, const T *__restrict__ ws,
-                                                        const T *__restrict__ wy, const T *__restrict__ zero,
-                                                        int64_t ldw, int m, int head, int col, int c0,
-                                                        const uint64_t *__restrict__ lmask, QnCoef<MC, K> cf,
+__global__ __launch_bounds__(BLOCK) void qn_draw_kernel(int64_t n, QN_TILE_PARAMS(T), QnCoef<MC, K> cf,
                                                         uint64_t seed, int64_t row0, int64_t s0, int first,
                                                         const T *__restrict__ mean, QnOuts<T> out) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
+  const QnTile<T> t = QN_TILE_VIEW(T);
   for_rows<T, V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
     const int64_t s = qn_slot<CW>(lmask, i);
     double x[K][W], a[MC][W], b[MC][W];
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
-      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
-    }
+    qn_ld_tile<T, MC, W, NT>(t, s, a, b);
     if (first) {
       double mu[W];
 #pragma unroll
@@ -119,28 +96,13 @@ __global__ __launch_bounds__(BLOCK) void qn_draw_kernel(int64_t n, const T *__re
     for (int kk = 0; kk < K; ++kk) {
       double o[W];
 #pragma unroll
-      for (int w = 0; w < W; ++w) {
-        double e = x[kk][w];
-#pragma unroll
-        for (int j = 0; j < MC; ++j) {
-          e += cf.c[kk][j] * a[j][w];
-          e += cf.c[kk][MC + j] * b[j][w];
-        }
-        o[w] = e;
-      }
+      for (int w = 0; w < W; ++w) o[w] = qn_comb<MC, W>(x[kk][w], cf, kk, a, b, w);
       stnt<W>(out.p[kk] + i, o);
     }
   });
 }
 
 // ---------------------------------------------------------------- launches (dispatch: k_qn_common.hpp)
-namespace {
-// blocks of 1, 2 or 4 samples; a block of more than one sample is whole pairs
-bool draw_block_ok(int mc, int k, int64_t s0) {
-  return qn_block_ok(mc, k) && s0 >= 0 && (k == 1 || (s0 & 1) == 0);
-}
-}  // namespace
-
 template <typename T>
 hipError_t launch_qn_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                          uint64_t seed, int64_t row0, int64_t s0, bool zz, double *part, double *res) {
@@ -154,8 +116,8 @@ hipError_t launch_qn_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int c
     // (the grid of the PLAIN kernel for both: the grid decides every workgroup's rows, hence the partial sums, and
     //  the two code objects need not be resident in the same numbers)
     g = grid_for_w(q, n, V, (const void *)qn_wtz_kernel<T, MC, K, V, CW, NT>);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, seed, row0, s0, part);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), seed, row0, s0,
+                       part);
   }))));
   return launch_qn_finalize(q, part, g, 2 * mc * k + (zz ? k : 0), res);
 }
@@ -166,15 +128,14 @@ hipError_t launch_qn_draw(const Queue &q, int64_t n, WStore<T> w, int head, int 
                           const T *mean, QnOuts<T> out) {
   if (!draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
   // (out / mean that are not 16-byte aligned: one row per lane)
-  bool vec2 = 2 * mc * k <= 20 && (!mean || aligned_for(mean, 2));
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for((const T *)out.p[kk], 2);
+  const bool vec2 = 2 * mc * k <= 20 && (!mean || aligned_for(mean, 2)) && all_aligned_for(out.p, k, 2);
   bool done = false;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
     const QnCoef<MC, K> cf = qn_coef_args<MC, K>(coef, alpha);
     auto kern = qn_draw_kernel<T, MC, K, V, CW, NT>;
     const int g = grid_for_w(q, n, V, (const void *)kern);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, cf, seed, row0, s0, first ? 1 : 0, first ? mean : (const T *)nullptr, out);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), cf, seed, row0, s0,
+                       first ? 1 : 0, first ? mean : (const T *)nullptr, out);
     done = true;
   }))));
   if (!done) return hipErrorInvalidValue;

@@ -16,12 +16,11 @@
 namespace lbk {
 
 template <typename T, int MC, bool CW, bool NT, bool ACC, int R>
-__global__ __launch_bounds__(BLOCK) void qn_basis_kernel(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                         const T *__restrict__ zero, int64_t ldw, int m, int head,
-                                                         int col, int c0, const uint64_t *__restrict__ lmask,
+__global__ __launch_bounds__(BLOCK) void qn_basis_kernel(int64_t n, QN_TILE_PARAMS(T),
                                                          const double *__restrict__ coef, int k, T *__restrict__ out,
                                                          int64_t ldo) {
   constexpr int D = 2 * MC;
+  const QnTile<T> t = QN_TILE_VIEW(T);
   const int lane = (int)(threadIdx.x & 63);
   const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
   const int64_t step = ((int64_t)gridDim.x * BLOCK >> 6) * (64 * R);
@@ -29,21 +28,7 @@ __global__ __launch_bounds__(BLOCK) void qn_basis_kernel(int64_t n, const T *__r
     int64_t row[R];
     bool live[R];
     double w[D][R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      row[r] = base + lane + 64 * r;
-      live[r] = row[r] < n;
-      // (a lane past the last row reads the zero line: every load unconditional, none out of bounds)
-      const int64_t s = live[r] ? qn_slot<CW>(lmask, row[r]) : 0;
-#pragma unroll
-      for (int j = 0; j < MC; ++j) {
-        const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-        double a[1], b[1];
-        ld_col<T, 1, NT>(live[r] && c0 + j < col, ws + off, zero, a);
-        ld_col<T, 1, NT>(live[r] && c0 + j < col, wy + off, zero, b);
-        w[j][r] = a[0], w[MC + j][r] = b[0];
-      }
-    }
+    qn_ld_rows<T, MC, CW, NT, R>(t, n, base, lane, row, live, w);
     for (int j = 0; j < k; ++j) {
       double acc[R];
 #pragma unroll
@@ -82,8 +67,8 @@ hipError_t launch_qn_basis(const Queue &q, int64_t n, WStore<T> w, int head, int
       constexpr int R = QN_BASIS_ROWS;
       auto kern = qn_basis_kernel<T, MC, CW, NT, ACC, R>;
       const int g = grid_for_w(q, (n + R - 1) / R, 1, (const void *)kern);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                         w.lmask, coef, k, out, ldo);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), coef, k, out,
+                         ldo);
       done = true;
     }
   }))));

@@ -56,16 +56,14 @@ hipError_t launch_qn_rows(const Queue &q, int64_t n, int64_t row0, WStore<T> w, 
 // dterm (k) and idx (k global rows) are uniform over the wave: scalar loads.  WGT: the sums are weighed by wgt, and a
 // row with wgt = 0 stores +0 on the first tile (and keeps it on the later ones: +0 + 0).
 template <typename T, int MC, bool CW, bool WGT, bool NT, bool ACC, int R>
-__global__ __launch_bounds__(BLOCK) void qn_cols_kernel(int64_t n, int64_t row0, const T *__restrict__ ws,
-                                                        const T *__restrict__ wy, const T *__restrict__ zero,
-                                                        int64_t ldw, int m, int head, int col, int c0,
-                                                        const uint64_t *__restrict__ lmask,
+__global__ __launch_bounds__(BLOCK) void qn_cols_kernel(int64_t n, int64_t row0, QN_TILE_PARAMS(T),
                                                         const double *__restrict__ coef,
                                                         const double *__restrict__ dterm,
                                                         const int64_t *__restrict__ idx,
                                                         const double *__restrict__ wgt, int k, T *__restrict__ out,
                                                         int64_t ldo) {
   constexpr int D = 2 * MC;
+  const QnTile<T> t = QN_TILE_VIEW(T);
   const int lane = (int)(threadIdx.x & 63);
   const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
   const int64_t step = ((int64_t)gridDim.x * BLOCK >> 6) * (64 * R);
@@ -73,22 +71,11 @@ __global__ __launch_bounds__(BLOCK) void qn_cols_kernel(int64_t n, int64_t row0,
     int64_t row[R];
     bool live[R];
     double w[D][R], f[R];
+    qn_ld_rows<T, MC, CW, NT, R>(t, n, base, lane, row, live, w);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      row[r] = base + lane + 64 * r;
-      live[r] = row[r] < n;
-      // (a lane past the last row reads the zero line: every load unconditional, none out of bounds)
-      const int64_t s = live[r] ? qn_slot<CW>(lmask, row[r]) : 0;
       f[r] = 1.0;
       if constexpr (WGT) f[r] = wgt[live[r] ? row[r] : 0];
-#pragma unroll
-      for (int j = 0; j < MC; ++j) {
-        const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-        double a[1], b[1];
-        ld_col<T, 1, NT>(live[r] && c0 + j < col, ws + off, zero, a);
-        ld_col<T, 1, NT>(live[r] && c0 + j < col, wy + off, zero, b);
-        w[j][r] = a[0], w[MC + j][r] = b[0];
-      }
     }
     for (int j = 0; j < k; ++j) {
       double acc[R];
@@ -131,8 +118,8 @@ hipError_t launch_qn_cols(const Queue &q, int64_t n, int64_t row0, WStore<T> w, 
       constexpr int R = QN_COLS_ROWS;
       auto kern = qn_cols_kernel<T, MC, CW, WGT, NT, ACC, R>;
       const int g = grid_for_w(q, (n + R - 1) / R, 1, (const void *)kern);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, row0, w.ws, w.wy, w.zero, w.ld, w.m, head, col,
-                         c0, w.lmask, coef, dterm, idx, wgt, k, out, ldo);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, row0, QN_TILE_ARGS(w, head, col, c0), coef, dterm,
+                         idx, wgt, k, out, ldo);
       done = true;
     }
   })))));

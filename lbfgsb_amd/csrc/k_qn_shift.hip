@@ -64,12 +64,10 @@ __device__ __forceinline__ void qn_weigh(const double (&wg)[W], double (&x)[W]) 
 // sums: slot kk * 2MC + j = S(:, c0 + j)'(w o v_kk), slot kk * 2MC + MC + j = Y(:, c0 + j)'(w o v_kk); VSLOT as in
 // qn_wtv_body (the weights stay in natural order).  ROOT: sqrt(w) in place of w
 template <typename T, int MC, int K, int V, bool CW, bool VSLOT, bool NT, bool ROOT>
-__global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, const T *__restrict__ ws,
-                                                             const T *__restrict__ wy, const T *__restrict__ zero,
-                                                             int64_t ldw, int m, int head, int col, int c0,
-                                                             const uint64_t *__restrict__ lmask, QnVecs<T> v,
+__global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, QN_TILE_PARAMS(T), QnVecs<T> v,
                                                              const double *__restrict__ wgt, double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
+  const QnTile<T> t = QN_TILE_VIEW(T);
   constexpr int NACC = 2 * MC * K;
   double acc[NACC];
 #pragma unroll
@@ -81,12 +79,7 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, const T 
     ldx<W, NT>(wgt + i, wg);
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) ldx<W, NT>(v.p[kk] + (VSLOT ? s : i), vv[kk]);
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
-      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
-    }
+    qn_ld_tile<T, MC, W, NT>(t, s, a, b);
     if constexpr (ROOT) {
 #pragma unroll
       for (int w = 0; w < W; ++w) wg[w] = sqrt(wg[w]);
@@ -95,13 +88,7 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, const T 
     for (int kk = 0; kk < K; ++kk) qn_weigh<W>(wg, vv[kk]);
 #pragma unroll
     for (int kk = 0; kk < K; ++kk)
-#pragma unroll
-      for (int j = 0; j < MC; ++j)
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          acc[kk * 2 * MC + j] += a[j][w] * vv[kk][w];
-          acc[kk * 2 * MC + MC + j] += b[j][w] * vv[kk][w];
-        }
+      qn_dot_acc<MC, W>(acc + kk * 2 * MC, a, b, vv[kk]);
   });
   block_reduce_store<NACC>(acc, NACC, 0, 0, part, MAX_BLOCKS);
 }
@@ -110,10 +97,7 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtv_kernel(int64_t n, const T 
 // else (a later column tile, src = out): out_kk[i] = src_kk[i] + w_i (the sum)
 // ROOT, first: out_kk[i] = sqrt(w_i) src_kk[i] + w_i (the sum), +0 where w_i = 0; the later tiles as above
 template <typename T, int MC, int K, int V, bool CW, bool NT, bool ROOT>
-__global__ __launch_bounds__(BLOCK) void qn_shift_expand_kernel(int64_t n, const T *__restrict__ ws,
-                                                                const T *__restrict__ wy, const T *__restrict__ zero,
-                                                                int64_t ldw, int m, int head, int col, int c0,
-                                                                const uint64_t *__restrict__ lmask, QnCoef<MC, K> cf,
+__global__ __launch_bounds__(BLOCK) void qn_shift_expand_kernel(int64_t n, QN_TILE_PARAMS(T), QnCoef<MC, K> cf,
                                                                 QnVecs<T> src, const double *__restrict__ wgt,
                                                                 int first, QnOuts<T> out) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
@@ -124,6 +108,8 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_expand_kernel(int64_t n, const
     ldx<W, NT>(wgt + i, wg);
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) ldx<W, false>(src.p[kk] + i, x[kk]);
+    // (loads and sum written out, as in qn_expand_kernel: with qn_ld_tile and qn_comb the REAL32 ROOT instantiation
+    //  <float, 10, 4, 2> went from 128 to 130 registers, which is 4 waves per SIMD to 3)
 #pragma unroll
     for (int j = 0; j < MC; ++j) {
       const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
@@ -168,27 +154,15 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_diag_kernel(int64_t n, const T
   __shared__ double sn[NP];
   for (int e = threadIdx.x; e < NP; e += BLOCK) sn[e] = np[e];
   __syncthreads();
+  const QnTile<T> t{ws, wy, zero, ldw, m, head, col, 0, lmask};
   for_rows<T, 1>(n, [&](int64_t i, auto) {
     // (N stays in LDS: see qn_diag_kernel)
     asm volatile("" ::: "memory");
     const int64_t s = qn_slot<CW>(lmask, i);
     double r[D][1], wg[1];
     ldx<1, NT>(wgt + i, wg);
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(j, col, head, m, ldw) + s;
-      ld_col<T, 1, NT>(j < col, ws + off, zero, r[j]);
-      ld_col<T, 1, NT>(j < col, wy + off, zero, r[MC + j]);
-    }
-    double acc = 0.0;
-    int e = 0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-      double t = 0.0;
-#pragma unroll
-      for (int b = a; b < D; ++b) t += sn[e++] * r[b][0];
-      acc += r[a][0] * t;
-    }
+    qn_ld_tile<T, MC, 1, NT>(t, s, r, r + MC);
+    const double acc = qn_rnr<MC>(sn, r);
     const double o[1] = {wg[0] == 0.0 ? 0.0 : wg[0] + wg[0] * wg[0] * acc};
     stnt<1>(out + i, o);
   });
@@ -214,16 +188,14 @@ hipError_t launch_qn_shift_wtv(const Queue &q, int64_t n, WStore<T> w, int head,
                                QnVecs<T> v, bool vslot, bool root, const double *wgt, double *part, double *res) {
   if (!qn_block_ok(mc, k) || (vslot && root)) return hipErrorInvalidValue;
   // (two rows per lane where qn_wtv has them; the weights add 2 V registers to its operands)
-  bool vec2 = !vslot && 2 * mc * k <= 20 && aligned_for(wgt, 2);
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
+  const bool vec2 = !vslot && 2 * mc * k <= 20 && aligned_for(wgt, 2) && all_aligned_for(v.p, k, 2);
   int g = 0;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT,
       QN_DISPATCH_BOOL(vslot, VS, QN_DISPATCH_BOOL(root, ROOT, {
     if constexpr ((!VS || V == 1) && !(VS && ROOT)) {
       auto kern = qn_shift_wtv_kernel<T, MC, K, V, CW, VS, NT, ROOT>;
       g = grid_for_w(q, n, V, (const void *)kern);
-      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                         w.lmask, v, wgt, part);
+      hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), v, wgt, part);
     }
   }))))));
   return launch_qn_finalize(q, part, g, 2 * mc * k, res);
@@ -234,15 +206,15 @@ hipError_t launch_qn_shift_expand(const Queue &q, int64_t n, WStore<T> w, int he
                                   const double *coef, QnVecs<T> src, const double *wgt, bool first, bool root,
                                   QnOuts<T> out) {
   if (!qn_block_ok(mc, k)) return hipErrorInvalidValue;
-  bool vec2 = 2 * mc * k <= 20 && aligned_for(wgt, 2);
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(src.p[kk], 2) && aligned_for((const T *)out.p[kk], 2);
+  const bool vec2 =
+      2 * mc * k <= 20 && aligned_for(wgt, 2) && all_aligned_for(src.p, k, 2) && all_aligned_for(out.p, k, 2);
   bool done = false;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, QN_DISPATCH_BOOL(root, ROOT, {
     const QnCoef<MC, K> cf = qn_coef_args<MC, K>(coef, 1.0);
     auto kern = qn_shift_expand_kernel<T, MC, K, V, CW, NT, ROOT>;
     const int g = grid_for_w(q, n, V, (const void *)kern);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, cf, src, wgt, first ? 1 : 0, out);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), cf, src, wgt,
+                       first ? 1 : 0, out);
     done = true;
   })))));
   if (!done) return hipErrorInvalidValue;

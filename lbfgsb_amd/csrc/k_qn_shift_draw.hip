@@ -24,11 +24,8 @@ namespace lbk {
 // The W'z sums of the two kernels agree bit for bit (see qn_wtz_body: the same grid, the same side of
 // block_reduce_store's scatter threshold).
 template <typename T, int MC, int K, int V, bool CW, bool NT, bool ZZ>
-__device__ __forceinline__ void qn_shift_wtz_body(int64_t n, const T *__restrict__ ws, const T *__restrict__ wy,
-                                                  const T *__restrict__ zero, int64_t ldw, int m, int head, int col,
-                                                  int c0, const uint64_t *__restrict__ lmask, uint64_t seed,
-                                                  int64_t row0, int64_t s0, const double *__restrict__ wgt,
-                                                  double *part) {
+__device__ __forceinline__ void qn_shift_wtz_body(int64_t n, const QnTile<T> &t, uint64_t seed, int64_t row0,
+                                                  int64_t s0, const double *__restrict__ wgt, double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
   constexpr int NW = 2 * MC * K, NACC = NW + (ZZ ? K : 0);
   static_assert((NW >= 16) == (NACC >= 16), "block_reduce_store reduces the W'z slots as the plain pass does");
@@ -37,15 +34,10 @@ __device__ __forceinline__ void qn_shift_wtz_body(int64_t n, const T *__restrict
   for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
   for_rows<T, V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
-    const int64_t s = qn_slot<CW>(lmask, i);
+    const int64_t s = qn_slot<CW>(t.lmask, i);
     double a[MC][W], b[MC][W], wg[W];
     ldx<W, NT>(wgt + i, wg);
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
-      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
-    }
+    qn_ld_tile<T, MC, W, NT>(t, s, a, b);
 #pragma unroll
     for (int w = 0; w < W; ++w) {
       double z[K];
@@ -55,6 +47,7 @@ __device__ __forceinline__ void qn_shift_wtz_body(int64_t n, const T *__restrict
 #pragma unroll
       for (int kk = 0; kk < K; ++kk) {
         const double zw = fr ? rw * z[kk] : 0.0;
+        // (written out, not qn_dot_acc: through it qn_shift_wtz_kernel<float, 5, 4, 2> went from 161 to 217 registers)
 #pragma unroll
         for (int j = 0; j < MC; ++j) {
           acc[kk * 2 * MC + j] += a[j][w] * zw;
@@ -68,50 +61,35 @@ __device__ __forceinline__ void qn_shift_wtz_body(int64_t n, const T *__restrict
 }
 
 template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_shift_wtz_kernel(int64_t n, const T *__restrict__ ws,
-                                                             const T *__restrict__ wy, const T *__restrict__ zero,
-                                                             int64_t ldw, int m, int head, int col, int c0,
-                                                             const uint64_t *__restrict__ lmask, uint64_t seed,
-                                                             int64_t row0, int64_t s0,
-                                                             const double *__restrict__ wgt, double *part) {
-  qn_shift_wtz_body<T, MC, K, V, CW, NT, false>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, seed, row0, s0, wgt,
-                                                part);
+__global__ __launch_bounds__(BLOCK) void qn_shift_wtz_kernel(int64_t n, QN_TILE_PARAMS(T), uint64_t seed,
+                                                             int64_t row0, int64_t s0, const double *__restrict__ wgt,
+                                                             double *part) {
+  qn_shift_wtz_body<T, MC, K, V, CW, NT, false>(n, QN_TILE_VIEW(T), seed, row0, s0, wgt, part);
 }
 
 template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_shift_wtzz_kernel(int64_t n, const T *__restrict__ ws,
-                                                              const T *__restrict__ wy, const T *__restrict__ zero,
-                                                              int64_t ldw, int m, int head, int col, int c0,
-                                                              const uint64_t *__restrict__ lmask, uint64_t seed,
-                                                              int64_t row0, int64_t s0,
-                                                              const double *__restrict__ wgt, double *part) {
-  qn_shift_wtz_body<T, MC, K, V, CW, NT, true>(n, ws, wy, zero, ldw, m, head, col, c0, lmask, seed, row0, s0, wgt,
-                                               part);
+__global__ __launch_bounds__(BLOCK) void qn_shift_wtzz_kernel(int64_t n, QN_TILE_PARAMS(T), uint64_t seed,
+                                                              int64_t row0, int64_t s0, const double *__restrict__ wgt,
+                                                              double *part) {
+  qn_shift_wtz_body<T, MC, K, V, CW, NT, true>(n, QN_TILE_VIEW(T), seed, row0, s0, wgt, part);
 }
 
 // first (tile c0 = 0): out_kk[i] = mean[i] + (cf.alpha sqrt(w_i) z_kk[i] + w_i sum_j (cf.c[kk][j] S(i, j) +
 // cf.c[kk][MC + j] Y(i, j))) with mean[i] = 0 for a NULL mean, and mean[i] itself where w_i = 0; later tiles:
 // out_kk[i] += w_i (the sum over the columns c0 + j), nothing where w_i = 0
 template <typename T, int MC, int K, int V, bool CW, bool NT>
-__global__ __launch_bounds__(BLOCK) void qn_shift_draw_kernel(int64_t n, const T *__restrict__ ws,
-                                                              const T *__restrict__ wy, const T *__restrict__ zero,
-                                                              int64_t ldw, int m, int head, int col, int c0,
-                                                              const uint64_t *__restrict__ lmask, QnCoef<MC, K> cf,
+__global__ __launch_bounds__(BLOCK) void qn_shift_draw_kernel(int64_t n, QN_TILE_PARAMS(T), QnCoef<MC, K> cf,
                                                               uint64_t seed, int64_t row0, int64_t s0, int first,
                                                               const T *__restrict__ mean,
                                                               const double *__restrict__ wgt, QnOuts<T> out) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
+  const QnTile<T> t = QN_TILE_VIEW(T);
   for_rows<T, V>(n, [&](int64_t i, auto wt) {
     constexpr int W = decltype(wt)::value;
     const int64_t s = qn_slot<CW>(lmask, i);
     double x[K][W], a[MC][W], b[MC][W], wg[W];
     ldx<W, NT>(wgt + i, wg);
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
-      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
-    }
+    qn_ld_tile<T, MC, W, NT>(t, s, a, b);
     double zs[K][W];  // first: cf.alpha sqrt(w) z; later tiles: not used
     if (first) {
       double mu[W];
@@ -139,12 +117,7 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_draw_kernel(int64_t n, const T
       double o[W];
 #pragma unroll
       for (int w = 0; w < W; ++w) {
-        double e = 0.0;
-#pragma unroll
-        for (int j = 0; j < MC; ++j) {
-          e += cf.c[kk][j] * a[j][w];
-          e += cf.c[kk][MC + j] * b[j][w];
-        }
+        const double e = qn_comb<MC, W>(0.0, cf, kk, a, b, w);
         o[w] = wg[w] == 0.0 ? x[kk][w] : x[kk][w] + (zs[kk][w] + wg[w] * e);
       }
       stnt<W>(out.p[kk] + i, o);
@@ -156,13 +129,11 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_draw_kernel(int64_t n, const T
 // center (CEN) and f = (w != 0); DD: K more sums, of q_kk[i]^2 / w_i over the rows with w_i != 0, in the slots
 // 2MC K + kk.  Whatever v or the center hold on a pinned row (a NaN too) contributes +0.
 template <typename T, int MC, int K, int V, bool CW, bool NT, bool CEN, bool DD>
-__global__ __launch_bounds__(BLOCK) void qn_shift_wtd_kernel(int64_t n, const T *__restrict__ ws,
-                                                             const T *__restrict__ wy, const T *__restrict__ zero,
-                                                             int64_t ldw, int m, int head, int col, int c0,
-                                                             const uint64_t *__restrict__ lmask, QnVecs<T> v,
+__global__ __launch_bounds__(BLOCK) void qn_shift_wtd_kernel(int64_t n, QN_TILE_PARAMS(T), QnVecs<T> v,
                                                              const T *__restrict__ center,
                                                              const double *__restrict__ wgt, double *part) {
   static_assert(!CW || V == 1, "the layout is read one row per lane");
+  const QnTile<T> t = QN_TILE_VIEW(T);
   constexpr int NW = 2 * MC * K, NACC = NW + (DD ? K : 0);
   double acc[NACC];
 #pragma unroll
@@ -176,12 +147,7 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtd_kernel(int64_t n, const T 
     for (int kk = 0; kk < K; ++kk) ldx<W, NT>(v.p[kk] + i, vv[kk]);
     double cc[CEN ? W : 1];
     if constexpr (CEN) ldx<W, NT>(center + i, cc);
-#pragma unroll
-    for (int j = 0; j < MC; ++j) {
-      const int64_t off = col_off(c0 + j, col, head, m, ldw) + s;
-      ld_col<T, W, NT>(c0 + j < col, ws + off, zero, a[j]);
-      ld_col<T, W, NT>(c0 + j < col, wy + off, zero, b[j]);
-    }
+    qn_ld_tile<T, MC, W, NT>(t, s, a, b);
 #pragma unroll
     for (int kk = 0; kk < K; ++kk)
 #pragma unroll
@@ -190,6 +156,8 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtd_kernel(int64_t n, const T 
         if constexpr (CEN) qd -= cc[w];
         vv[kk][w] = wg[w] == 0.0 ? 0.0 : qd;
       }
+    // (written out, not qn_dot_acc: through it the REAL32 K = 1 instantiations with the norms along lost a wave per
+    //  SIMD -- <float, 10, 1, 2, ..., DD> 126 -> 142 registers, <float, 5, 1, 2, ..., DD> 78 -> 82)
 #pragma unroll
     for (int kk = 0; kk < K; ++kk)
 #pragma unroll
@@ -210,18 +178,11 @@ __global__ __launch_bounds__(BLOCK) void qn_shift_wtd_kernel(int64_t n, const T 
 }
 
 // ---------------------------------------------------------------- launches (dispatch: k_qn_common.hpp)
-namespace {
-// blocks of 1, 2 or 4 samples; a block of more than one sample is whole pairs
-bool shift_draw_block_ok(int mc, int k, int64_t s0) {
-  return qn_block_ok(mc, k) && s0 >= 0 && (k == 1 || (s0 & 1) == 0);
-}
-}  // namespace
-
 template <typename T>
 hipError_t launch_qn_shift_wtz(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                                uint64_t seed, int64_t row0, int64_t s0, bool zz, const double *wgt, double *part,
                                double *res) {
-  if (!shift_draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
+  if (!draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
   // (two rows per lane where qn_wtz has them and the weights are 16-byte aligned: they add 2 V registers)
   const bool vec2 = 2 * mc * k <= 20 && aligned_for(wgt, 2);
   int g = 0;
@@ -229,8 +190,8 @@ hipError_t launch_qn_shift_wtz(const Queue &q, int64_t n, WStore<T> w, int head,
     auto kern = zz ? qn_shift_wtzz_kernel<T, MC, K, V, CW, NT> : qn_shift_wtz_kernel<T, MC, K, V, CW, NT>;
     // (the grid of the PLAIN kernel for both, as launch_qn_wtz: the grid decides every workgroup's rows)
     g = grid_for_w(q, n, V, (const void *)qn_shift_wtz_kernel<T, MC, K, V, CW, NT>);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, seed, row0, s0, wgt, part);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), seed, row0, s0, wgt,
+                       part);
   }))));
   return launch_qn_finalize(q, part, g, 2 * mc * k + (zz ? k : 0), res);
 }
@@ -239,17 +200,17 @@ template <typename T>
 hipError_t launch_qn_shift_draw(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
                                 const double *coef, double alpha, uint64_t seed, int64_t row0, int64_t s0,
                                 bool first, const T *mean, const double *wgt, QnOuts<T> out) {
-  if (!shift_draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
+  if (!draw_block_ok(mc, k, s0)) return hipErrorInvalidValue;
   // (out / mean that are not 16-byte aligned: one row per lane)
-  bool vec2 = 2 * mc * k <= 20 && aligned_for(wgt, 2) && (!mean || aligned_for(mean, 2));
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for((const T *)out.p[kk], 2);
+  const bool vec2 =
+      2 * mc * k <= 20 && aligned_for(wgt, 2) && (!mean || aligned_for(mean, 2)) && all_aligned_for(out.p, k, 2);
   bool done = false;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT, {
     const QnCoef<MC, K> cf = qn_coef_args<MC, K>(coef, alpha);
     auto kern = qn_shift_draw_kernel<T, MC, K, V, CW, NT>;
     const int g = grid_for_w(q, n, V, (const void *)kern);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, cf, seed, row0, s0, first ? 1 : 0, first ? mean : (const T *)nullptr, wgt, out);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), cf, seed, row0, s0,
+                       first ? 1 : 0, first ? mean : (const T *)nullptr, wgt, out);
     done = true;
   }))));
   if (!done) return hipErrorInvalidValue;
@@ -261,15 +222,15 @@ hipError_t launch_qn_shift_wtd(const Queue &q, int64_t n, WStore<T> w, int head,
                                QnVecs<T> v, const T *center, bool dd, const double *wgt, double *part, double *res) {
   if (!qn_block_ok(mc, k)) return hipErrorInvalidValue;
   // (two rows per lane as launch_qn_wtv's centred pass, the weights 2 V registers more)
-  bool vec2 = 2 * mc * k <= 20 && aligned_for(wgt, 2) && (!center || aligned_for(center, 2));
-  for (int kk = 0; kk < k; ++kk) vec2 = vec2 && aligned_for(v.p[kk], 2);
+  const bool vec2 =
+      2 * mc * k <= 20 && aligned_for(wgt, 2) && (!center || aligned_for(center, 2)) && all_aligned_for(v.p, k, 2);
   int g = 0;
   QN_DISPATCH_MC(mc, QN_DISPATCH_K(k, QN_DISPATCH_CW(w.lmask, QN_DISPATCH_BOOL(q.nt, NT,
       QN_DISPATCH_BOOL(center != nullptr, CEN, QN_DISPATCH_BOOL(dd, DD, {
     auto kern = qn_shift_wtd_kernel<T, MC, K, V, CW, NT, CEN, DD>;
     g = grid_for_w(q, n, V, (const void *)kern);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, w.ws, w.wy, w.zero, w.ld, w.m, head, col, c0,
-                       w.lmask, v, center, wgt, part);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), 0, q.stream, n, QN_TILE_ARGS(w, head, col, c0), v, center, wgt,
+                       part);
   }))))));
   return launch_qn_finalize(q, part, g, 2 * mc * k + (dd ? k : 0), res);
 }

@@ -8,6 +8,7 @@
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 namespace lbk {
@@ -25,6 +26,13 @@ constexpr int qn_piece_k(int left, int mc) {
 }
 // a block that a launch accepts: what qn_piece_k can return
 constexpr bool qn_block_ok(int mc, int k) { return k >= 1 && qn_piece_k(k, mc) == k; }
+// The k vectors of an operator call go through its two passes in blocks of at most QN_KMAX: the width of the block
+// that starts at vector k0.  s0: for the draws the sample the block starts at (first + k0) -- a block of more than one
+// sample is whole pairs of the generator, so an odd first sample goes alone and every later block starts at an even
+// one; 0 for vectors that are loaded.
+constexpr int qn_block_kc(int64_t k0, int64_t k, int64_t s0 = 0) {
+  return (s0 & 1) ? 1 : (int)(k - k0 < QN_KMAX ? k - k0 : QN_KMAX);
+}
 
 // what the launches of the first tile carry behind their W'V sums: nothing, the k squared norms of the piece's
 // vectors (quadratic forms, draw densities), or the k (k + 1) / 2 sums d_a'd_b, a <= b, row by row (Gram matrices)

@@ -8,7 +8,10 @@
 // log-densities (lbfgsb_hip_qn_shift_sqrt / _draw / _quad / _logpdf; k_qn_shift_draw.hip, section 10g).
 // Which launches a pass over W is made of and where their sums land is decided in one place, qn_plan.hpp (host-only,
 // walked on the CPU by tests/qn_plan_check.cpp): every W'V pass here goes through qn_sums_by on a plan, every
-// expansion through qn_expand_by, and a new operator hooks in with a plan and a launch of its own.
+// expansion through qn_expand_by, and the loops around them exist once: qn_blocks_by (the two passes of an operator,
+// block by block: apply, solve, the roots and the draws), qn_gram_by (the columns of W as the vectors: the three
+// Grams), qn_quad_sums (the quadratic forms) and qn_upload_n (the packed N of the diagonals).  A new operator hooks in
+// with its launches and its coefficient map.
 //
 // The entries read the pairs of the last return (or import) and nothing else of the iteration's state changes:
 // W is read in the layout it is in (Wc(), never W()), the sums go through buffers of their own (never q.d_part /
@@ -111,6 +114,19 @@
     return fail(LBFGSB_E_NOGPU, std::string("qn: launch of ") + what + " failed: " + hipGetErrorString(e));
   }
   using QnCarry = lbk::QnCarry;
+  using QnPiece = lbk::QnPiece;
+  using QnVecs = lbk::QnVecs<T>;
+  using QnOuts = lbk::QnOuts<T>;
+  // one launch on a piece, a failure reported under its name: launch_fn(q, n, W, head, col, c0, mc, k, args...)
+  template <typename F, typename... A>
+  int qn_go(const char *what, F launch_fn, const QnPiece &p, A... args) {
+    return qn_launched(launch_fn(q, n, Wc(), qn.head, qn.col, p.c0, p.mc, p.k, args...), what);
+  }
+  // ... of a W'V pass: its partials and the piece's slots of the result buffer come last
+  template <typename F, typename... A>
+  int qn_go_sums(const char *what, F launch_fn, const QnPiece &p, A... args) {
+    return qn_go(what, launch_fn, p, args..., qn.d_part, qn.d_res + p.off);
+  }
   double qn_alpha(bool inv) const { return inv ? 1.0 / qn.theta : qn.theta; }
   // One W'V pass by a plan of qn.col pairs (qn_plan.hpp): a launch per piece, one fetch of all their sums (all ranks
   // reduced), then [S'v_k; Y'v_k] -> out[k * 2 col + i] (i < col: S, else Y) and what the first tile's launches
@@ -120,7 +136,7 @@
   int qn_sums_by(const lbk::QnPlan &pl, double *out, double *carried, L &&launch) {
     // (<= qn_res(LBFGSB_MAX_M) for every col <= LBFGSB_MAX_M; checked before anything is written)
     if (pl.total > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");
-    for (const lbk::QnPiece &p : pl.pieces) CHK(launch(p));
+    for (const QnPiece &p : pl.pieces) CHK(launch(p));
     CHK(qn_reduce(pl.total));
     lbk::qn_scatter_sums(pl, qn.h_res.data(), out);
     lbk::qn_scatter_carry(pl, qn.h_res.data(), carried);
@@ -129,23 +145,10 @@
   // the pass for d_k = v_k - center (center may be NULL: the vectors as they are).  vslot: the vectors are columns of
   // W, read at their slots in its layout (no center, nothing carried)
   int qn_sums(const lbk::QnPlan &pl, const T *const *v, bool vslot, const T *center, double *out, double *carried) {
-    const lbk::WStore<T> w = Wc();
-    return qn_sums_by(pl, out, carried, [&](const lbk::QnPiece &p) {
-      lbk::QnVecs<T> vv{};
+    return qn_sums_by(pl, out, carried, [&](const QnPiece &p) {
+      QnVecs vv{};
       for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
-      return qn_launched(lbk::launch_qn_wtv<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, vv, vslot, center, p.carry,
-                                               qn.d_part, qn.d_res + p.off),
-                         "qn_wtv");
-    });
-  }
-  // the same with the vectors generated: the samples s0 .. s0 + kc - 1 of seed (s0 even unless kc = 1); the W'z sums
-  // are the same bits whether z_k'z_k is carried or not
-  int qn_sums_z(const lbk::QnPlan &pl, uint64_t seed, int64_t s0, double *out, double *zz) {
-    const lbk::WStore<T> w = Wc();
-    return qn_sums_by(pl, out, zz, [&](const lbk::QnPiece &p) {
-      return qn_launched(lbk::launch_qn_wtz<T>(q, n, w, qn.head, qn.col, p.c0, p.mc, p.k, seed, row0, s0 + p.k0,
-                                               p.carry == QnCarry::Norms, qn.d_part, qn.d_res + p.off),
-                         "qn_wtz");
+      return qn_go_sums("qn_wtv", lbk::launch_qn_wtv<T>, p, vv, vslot, center, p.carry);
     });
   }
   // The second pass of qn_apply and the draws: out_k (+)= [S, Y] cf_k tile by tile (with no pair one empty tile, which
@@ -153,30 +156,97 @@
   template <typename L>
   int qn_expand_by(int kc, const double *cf, L &&launch) {
     const lbk::QnPlan pl = lbk::qn_plan(qn.col, kc, QnCarry::None, true);
-    for (const lbk::QnPiece &p : pl.pieces) {
+    for (const QnPiece &p : pl.pieces) {
       double coef[2 * lbk::QN_TILE * lbk::QN_KMAX];
       lbk::qn_pack_coef(p, qn.col, cf, coef);
       CHK(launch(p, coef));
     }
     return 0;
   }
+  // the vectors of one piece of the block that starts at vector k0: columns of v, ldv apart
+  QnVecs qn_vecs(const QnPiece &p, const T *v, int64_t ldv, int64_t k0) const {
+    QnVecs vv{};
+    for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v + (k0 + p.k0 + kk) * ldv;
+    return vv;
+  }
+  // qn_expand_by for the block that starts at vector k0, into the columns of out (ldo apart): the first tile reads
+  // column j of v (ldv apart; ldv = 0: one vector for all; v NULL: nothing, the draws generate), a later tile reads
+  // what the earlier ones wrote.  launch(piece, coef, src, dst)
+  template <typename L>
+  int qn_expand_block(int64_t k0, int kc, const double *cf, const T *v, int64_t ldv, T *out, int64_t ldo, L &&launch) {
+    return qn_expand_by(kc, cf, [&](const QnPiece &p, const double *coef) {
+      QnVecs src{};
+      QnOuts dst{};
+      for (int kk = 0; kk < p.k; ++kk) {
+        dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
+        src.p[kk] = p.c0 > 0 ? dst.p[kk] : v ? v + (k0 + p.k0 + kk) * ldv : nullptr;
+      }
+      return launch(p, coef, src, dst);
+    });
+  }
+  // The two passes of an operator on k vectors, block by block (qn_plan.hpp, qn_block_kc; first: the first sample of
+  // a draw, 0 for vectors that are loaded): sums(k0, piece) launches one piece of the W'V pass of the block at k0
+  // -- with no pair it runs only for what it carries --, coef(j, sums, carried, c) maps [S'v; Y'v] of vector j and
+  // what was carried for it to its (cs; cy) on the host, and expand(k0, piece, coef, src, dst) launches one piece of
+  // the expansion (qn_expand_block).
+  template <typename S, typename C, typename E>
+  int qn_blocks_by(int64_t k, int64_t first, QnCarry carry, const T *v, int64_t ldv, T *out, int64_t ldo, S &&sums,
+                   C &&coef, E &&expand) {
+    const int col = qn.col;
+    std::vector<double> sm((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf(sm.size());
+    double carried[lbk::QN_KMAX] = {};
+    for (int64_t k0 = 0; k0 < k;) {
+      const int kc = lbk::qn_block_kc(k0, k, first + k0);
+      if (col > 0 || carry != QnCarry::None) {
+        CHK(qn_sums_by(lbk::qn_plan(col, kc, carry), sm.data(), carried,
+                       [&](const QnPiece &p) { return sums(k0, p); }));
+        for (int kk = 0; kk < kc; ++kk)
+          CHK(coef(k0 + kk, sm.data() + (size_t)kk * 2 * col, carried[kk], cf.data() + (size_t)kk * 2 * col));
+      }
+      CHK(qn_expand_block(k0, kc, cf.data(), v, ldv, out, ldo,
+                          [&](const QnPiece &p, const double *coef, QnVecs src, QnOuts dst) {
+                            return expand(k0, p, coef, src, dst);
+                          }));
+      k0 += kc;
+    }
+    return qn_finish();
+  }
+  // The columns j0 .. j1 - 1 of [S, Y] (j < col: S, else Y) as the vectors of a W'V pass, QN_KMAX at a time and read
+  // at their slots in W's layout: launch(piece, vectors) is one launch, put(j, sums) takes [S'w_j; Y'w_j] of column j
+  template <typename L, typename P>
+  int qn_gram_by(int j0, int j1, L &&launch, P &&put) {
+    const int col = qn.col;
+    std::vector<double> sums((size_t)2 * col * lbk::QN_KMAX);
+    for (int k0 = j0; k0 < j1; k0 += lbk::QN_KMAX) {
+      const int kc = std::min(lbk::QN_KMAX, j1 - k0);
+      CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::None), sums.data(), nullptr, [&](const QnPiece &p) {
+        QnVecs vv{};
+        for (int kk = 0; kk < p.k; ++kk) {
+          const int j = k0 + p.k0 + kk;
+          vv.p[kk] = (j < col ? ws : wy) + (int64_t)((qn.head - 1 + (j < col ? j : j - col)) % m) * ld;
+        }
+        return launch(p, vv);
+      }));
+      for (int kk = 0; kk < kc; ++kk) put(k0 + kk, sums.data() + (size_t)kk * 2 * col);
+    }
+    return 0;
+  }
+  // ... of the plain model: the pass of qn_sums on them
+  template <typename P>
+  int qn_gram_cols(int j0, int j1, P &&put) {
+    return qn_gram_by(j0, j1, [&](const QnPiece &p, QnVecs vv) {
+      return qn_go_sums("qn_wtv", lbk::launch_qn_wtv<T>, p, vv, true, nullptr, p.carry);
+    }, put);
+  }
   // S'Y and Y'Y over all rows, once per pair generation (the vectors of the W'V pass are the columns of Y)
   int qn_gram() {
     if (qn.gram_gen == qn.gen) return 0;
     const int col = qn.col;
     qn.sty.assign((size_t)col * col, 0.0), qn.yty.assign((size_t)col * col, 0.0);
-    std::vector<double> sums((size_t)2 * col * lbk::QN_KMAX);
-    for (int k0 = 0; k0 < col; k0 += lbk::QN_KMAX) {
-      const int kc = std::min(lbk::QN_KMAX, col - k0);
-      const T *v[lbk::QN_KMAX];
-      for (int kk = 0; kk < kc; ++kk) v[kk] = wy + (int64_t)((qn.head - 1 + k0 + kk) % m) * ld;
-      CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::None), v, true, nullptr, sums.data(), nullptr));
-      for (int kk = 0; kk < kc; ++kk)
-        for (int i = 0; i < col; ++i) {
-          qn.sty[i + (size_t)(k0 + kk) * col] = sums[(size_t)kk * 2 * col + i];
-          qn.yty[i + (size_t)(k0 + kk) * col] = sums[(size_t)kk * 2 * col + col + i];
-        }
-    }
+    CHK(qn_gram_cols(col, 2 * col, [&](int j, const double *sums) {
+      std::copy_n(sums, col, qn.sty.data() + (size_t)(j - col) * col);
+      std::copy_n(sums + col, col, qn.yty.data() + (size_t)(j - col) * col);
+    }));
     qn.gram_gen = qn.gen;
     if (qn.theta_gram && col > 0)  // matupd's theta = y'y / s'y of the newest pair (:2318)
       qn.theta = qn.yty[(size_t)(col - 1) * (col + 1)] / sy[(size_t)(col - 1) * (m + 1)];
@@ -190,15 +260,8 @@
     if (qn.sts_gen == qn.gen) return 0;
     const int col = qn.col;
     qn.sts.assign((size_t)col * col, 0.0);
-    std::vector<double> sums((size_t)2 * col * lbk::QN_KMAX);
-    for (int k0 = 0; k0 < col; k0 += lbk::QN_KMAX) {
-      const int kc = std::min(lbk::QN_KMAX, col - k0);
-      const T *v[lbk::QN_KMAX];
-      for (int kk = 0; kk < kc; ++kk) v[kk] = ws + (int64_t)((qn.head - 1 + k0 + kk) % m) * ld;
-      CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::None), v, true, nullptr, sums.data(), nullptr));
-      for (int kk = 0; kk < kc; ++kk)
-        for (int i = 0; i < col; ++i) qn.sts[i + (size_t)(k0 + kk) * col] = sums[(size_t)kk * 2 * col + i];
-    }
+    CHK(qn_gram_cols(0, col,
+                     [&](int j, const double *sums) { std::copy_n(sums, col, qn.sts.data() + (size_t)j * col); }));
     qn.sts_gen = qn.gen;
     return 0;
   }
@@ -224,6 +287,12 @@
     };
   }
 
+  // g (d x d, column-major) <- (g + g') / 2
+  static void qn_symmetrise(int d, double *g) {
+    for (int j = 0; j < d; ++j)
+      for (int i = 0; i < j; ++i)
+        g[i + (size_t)j * d] = g[j + (size_t)i * d] = 0.5 * (g[i + (size_t)j * d] + g[j + (size_t)i * d]);
+  }
   // N of the mode (as qn_diag forms it) and G = [S, Y]'[S, Y] from ss and the Gram (after qn_gram()), both 2col x 2col
   // (sts: S'S from qn_gram_ss in place of Ss)
   int qn_model_mats(bool inv, double *nm, double *g, const double *sts = nullptr) {
@@ -236,11 +305,7 @@
         g[i + (size_t)(col + j) * d] = g[(col + j) + (size_t)i * d] = qn.sty[i + (size_t)j * col];
         g[(col + i) + (size_t)(col + j) * d] = qn.yty[i + (size_t)j * col];
       }
-    for (int j = 0; j < d; ++j)  // (Y'Y as the Gram pass summed it: symmetric up to rounding)
-      for (int i = 0; i < j; ++i) {
-        const double v = 0.5 * (g[i + (size_t)j * d] + g[j + (size_t)i * d]);
-        g[i + (size_t)j * d] = g[j + (size_t)i * d] = v;
-      }
+    qn_symmetrise(d, g);  // (Y'Y as the Gram pass summed it: symmetric up to rounding)
     return 0;
   }
   // C of A^(1/2) = sqrt(alpha) I + [S, Y] C [S, Y]' and the log-det sum of B (inv = false) or H, once per pair
@@ -263,10 +328,10 @@
     qn.root_gen[md] = qn.gen;
     return 0;
   }
-  // c = f C sums for one vector (sums = [S'v; Y'v], 2col each)
-  void qn_root_map(bool inv, double f, const double *sums, double *c) const {
+  // c = f C sums for one vector: C (2col x 2col, column-major) of a root -- qn.root_c[mode], qsh.root_c -- and
+  // sums = [S'v; Y'v] as that root's W'V pass weighs them
+  void qn_root_map(const std::vector<double> &cm, double f, const double *sums, double *c) const {
     const int d = 2 * qn.col;
-    const double *cm = qn.root_c[inv ? 1 : 0].data();
     for (int i = 0; i < d; ++i) {
       double t = 0.0;
       for (int j = 0; j < d; ++j) t = t + cm[i + (size_t)j * d] * sums[j];
@@ -302,33 +367,24 @@
     CHK(qn_ready());
     const bool inv = mode == LBFGSB_QN_H;
     CHK(qn_root_coef(inv));
-    const int col = qn.col;
     const double lconst = h_logp ? qn_log_norm(inv, scale) : 0.0;
-    double zz[lbk::QN_KMAX];
     const double ra = std::sqrt(qn_alpha(inv));
-    const lbk::WStore<T> w = Wc();
     const T *mean = (const T *)mean_;
-    T *out = (T *)out_;
-    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf(sums.size());
-    for (int64_t k0 = 0; k0 < k;) {
-      const int64_t s0 = first + k0;
-      const int kc = (s0 & 1) ? 1 : (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
-      if (col > 0 || h_logp) {
-        CHK(qn_sums_z(lbk::qn_plan(col, kc, h_logp ? QnCarry::Norms : QnCarry::None), seed, s0, sums.data(), zz));
-        for (int kk = 0; kk < kc && col > 0; ++kk)
-          qn_root_map(inv, scale, sums.data() + (size_t)kk * 2 * col, cf.data() + (size_t)kk * 2 * col);
-        for (int kk = 0; kk < kc && h_logp; ++kk) h_logp[k0 + kk] = -0.5 * (lconst + zz[kk]);
-      }
-      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
-        lbk::QnOuts<T> dst{};
-        for (int kk = 0; kk < p.k; ++kk) dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
-        return qn_launched(lbk::launch_qn_draw<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef, scale * ra, seed,
-                                                  row0, s0 + p.k0, p.c0 == 0, mean, dst),
-                           "qn_draw");
-      }));
-      k0 += kc;
-    }
-    return qn_finish();
+    return qn_blocks_by(
+        k, first, h_logp ? QnCarry::Norms : QnCarry::None, nullptr, 0, (T *)out_, ldo,
+        [&](int64_t k0, const QnPiece &p) {
+          return qn_go_sums("qn_wtz", lbk::launch_qn_wtz<T>, p, seed, row0, first + k0 + p.k0,
+                            p.carry == QnCarry::Norms);
+        },
+        [&](int64_t j, const double *sums, double zz, double *c) {
+          qn_root_map(qn.root_c[inv ? 1 : 0], scale, sums, c);
+          if (h_logp) h_logp[j] = -0.5 * (lconst + zz);
+          return 0;
+        },
+        [&](int64_t k0, const QnPiece &p, const double *coef, QnVecs, QnOuts dst) {
+          return qn_go("qn_draw", lbk::launch_qn_draw<T>, p, coef, scale * ra, seed, row0, first + k0 + p.k0,
+                       p.c0 == 0, mean, dst);
+        });
   }
 
   // n_global log 2 pi + 2 n_global log |scale| + log det A (after qn_root_coef(inv))
@@ -336,19 +392,20 @@
     return (double)nglob * std::log(6.283185307179586476925) + 2.0 * (double)nglob * std::log(std::fabs(scale)) +
            qn_logdet_of(inv);
   }
-  // q_j = (v_j - center)' A (v_j - center) = alpha d'd + p'N p, p = [S, Y]'d: the W'V pass alone, d'd carried along
-  int qn_quad_by(bool inv, int64_t k, const T *v, int64_t ldv, const T *center, double *h_q) {
+  // q_j = norm(dd_j) + p_j'N p_j, p_j = [S, Y]'d_j, N of the mode, for the k vectors d_j = v_j - center: the W'd pass
+  // alone, nothing written.  launch(k0, piece): one piece of that pass for the block that starts at vector k0, with
+  // what the norm term is made of (dd_j) carried along; norm is asked after the Gram, which may set theta
+  template <typename L, typename F>
+  int qn_quad_sums(bool inv, int64_t k, double *h_q, L &&launch, F &&norm) {
     const int col = qn.col;
     if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
-    const double alpha = qn_alpha(inv);
     const std::vector<double> dg = qn_dg();
     std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), c((size_t)2 * std::max(col, 1));
     double dd[lbk::QN_KMAX];
     for (int64_t k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
-      const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
-      const T *vp[lbk::QN_KMAX];
-      for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (k0 + kk) * ldv;
-      CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::Norms), vp, false, center, sums.data(), dd));
+      const int kc = lbk::qn_block_kc(k0, k);
+      CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::Norms), sums.data(), dd,
+                     [&](const QnPiece &p) { return launch(k0, p); }));
       for (int kk = 0; kk < kc; ++kk) {
         const double *sv = sums.data() + (size_t)kk * 2 * col;
         double t = 0.0;  // p'(N p), S part then Y part, ascending
@@ -356,10 +413,19 @@
           CHK(qn_coef(inv, dg.data(), sv, sv + col, c.data(), c.data() + col));
           for (int i = 0; i < 2 * col; ++i) t = t + sv[i] * c[(size_t)i];
         }
-        h_q[k0 + kk] = alpha * dd[kk] + t;
+        h_q[k0 + kk] = norm(dd[kk]) + t;
       }
     }
     return 0;
+  }
+  // (v_j - center)' A (v_j - center) = alpha d'd + p'N p with d'd carried along
+  int qn_quad_by(bool inv, int64_t k, const T *v, int64_t ldv, const T *center, double *h_q) {
+    return qn_quad_sums(
+        inv, k, h_q,
+        [&](int64_t k0, const QnPiece &p) {
+          return qn_go_sums("qn_wtv", lbk::launch_qn_wtv<T>, p, qn_vecs(p, v, ldv, k0), false, center, p.carry);
+        },
+        [&](double dd) { return qn_alpha(inv) * dd; });
   }
   // d_a'd_b for every a of one piece and b of a later one: one vectors-only launch per pair of pieces, all of them
   // back to back and fetched with one wait (fewer than k^2 / 2 <= 2048 sums: they fit the result buffer together).
@@ -379,7 +445,7 @@
     if (jobs.empty()) return 0;
     if (off > QN_RES) return fail(LBFGSB_E_STATE, "qn: more sums than the buffer holds");  // (before any launch)
     for (const Job &j : jobs) {
-      lbk::QnVecs<T> va{}, vb{};
+      QnVecs va{}, vb{};
       for (int kk = 0; kk < j.ka; ++kk) va.p[kk] = v + (int64_t)(j.a0 + kk) * ldv;
       for (int kk = 0; kk < j.kb; ++kk) vb.p[kk] = v + (int64_t)(j.b0 + kk) * ldv;
       CHK(qn_launched(lbk::launch_qn_dtd<T>(q, n, va, j.ka, vb, j.kb, center, qn.d_part, qn.d_res + j.off),
@@ -409,7 +475,7 @@
       for (int kk = 0; kk < pl.kc; ++kk) vp[kk] = v + (int64_t)(k0 + kk) * ldv;
       double gr[lbk::QN_KMAX * lbk::QN_KMAX] = {};
       CHK(qn_sums(pl, vp, false, center, p.data() + (size_t)k0 * d, gr));
-      for (const lbk::QnPiece &pp : pl.pieces) {  // the pieces of the first tile: they carried their Grams
+      for (const QnPiece &pp : pl.pieces) {  // the pieces of the first tile: they carried their Grams
         if (pp.carry != QnCarry::Gram) continue;
         pc.emplace_back(k0 + pp.k0, pp.k);
         for (int a = pp.k0; a < pp.k0 + pp.k; ++a)
@@ -445,39 +511,38 @@
     if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
     const double alpha = root ? std::sqrt(qn_alpha(inv)) : qn_alpha(inv);
     const std::vector<double> dg = qn_dg();
-    const lbk::WStore<T> w = Wc();
     const T *v = (const T *)v_;
-    T *out = (T *)out_;
-    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf((size_t)2 * std::max(col, 1) * lbk::QN_KMAX);
-    for (int64_t k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
-      const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
-      const T *vp[lbk::QN_KMAX];
-      for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (k0 + kk) * ldv;
-      if (col > 0) {
-        CHK(qn_sums(lbk::qn_plan(col, kc, QnCarry::None), vp, false, nullptr, sums.data(), nullptr));
-        for (int kk = 0; kk < kc; ++kk) {
-          const double *sv = sums.data() + (size_t)kk * 2 * col;
-          double *c = cf.data() + (size_t)kk * 2 * col;
-          if (root) qn_root_map(inv, 1.0, sv, c);
-          else CHK(qn_coef(inv, dg.data(), sv, sv + col, c, c + col));
-        }
-      }
-      // out = alpha v + [S, Y] (cs; cy), one launch per column tile and block of vectors (col = 0: alpha v)
-      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
-        lbk::QnVecs<T> src{};
-        lbk::QnOuts<T> dst{};
-        for (int kk = 0; kk < p.k; ++kk) {
-          dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
-          src.p[kk] = p.c0 == 0 ? vp[p.k0 + kk] : dst.p[kk];
-        }
-        return qn_launched(lbk::launch_qn_expand<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef,
-                                                    p.c0 == 0 ? alpha : 1.0, src, dst),
-                           "qn_expand");
-      }));
-    }
-    return qn_finish();
+    // out = alpha v + [S, Y] (cs; cy), one launch per column tile and block of vectors (col = 0: alpha v)
+    return qn_blocks_by(
+        k, 0, QnCarry::None, v, ldv, (T *)out_, ldo,
+        [&](int64_t k0, const QnPiece &p) {
+          return qn_go_sums("qn_wtv", lbk::launch_qn_wtv<T>, p, qn_vecs(p, v, ldv, k0), false, nullptr, p.carry);
+        },
+        [&](int64_t, const double *sums, double, double *c) {
+          if (!root) return qn_coef(inv, dg.data(), sums, sums + col, c, c + col);
+          qn_root_map(qn.root_c[inv ? 1 : 0], 1.0, sums, c);
+          return 0;
+        },
+        [&](int64_t, const QnPiece &p, const double *coef, QnVecs src, QnOuts dst) {
+          return qn_go("qn_expand", lbk::launch_qn_expand<T>, p, coef, p.c0 == 0 ? alpha : 1.0, src, dst);
+        });
   }
 
+  // N of a coefficient map (lbh::qn_nmat; with no pair nothing of it), packed as the diagonal kernels read it, into
+  // d_n: the wait for the staging buffer, which may still feed an earlier copy, then the upload
+  template <typename M>
+  int qn_upload_n(M &&map, double *d_n) {
+    const int col = qn.col;
+    std::vector<double> nm((size_t)4 * col * col + 1);
+    if (col > 0) {
+      const int info = lbh::qn_nmat(col, map, nm.data());
+      if (info) return info;
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    lbh::qn_pack_n(col, lbk::maxc_for(std::max(col, 1)), nm.data(), qn.h_n);
+    HIPCHK(hipMemcpyAsync(d_n, qn.h_n, (size_t)QN_NP * sizeof(double), hipMemcpyHostToDevice, stream));
+    return 0;
+  }
   int qn_diag(int mode, void *out_) override {
     CHK(qn_ready());
     const bool inv = mode == LBFGSB_QN_H;
@@ -486,14 +551,7 @@
     if (col > 0 && (inv || qn.theta_gram)) CHK(qn_gram());
     const int md = inv ? 1 : 0;
     if (qn.n_gen[md] != qn.gen || col == 0) {
-      std::vector<double> nm((size_t)4 * col * col + 1);
-      if (col > 0) {
-        const int info = lbh::qn_nmat(col, qn_coef_map(inv), nm.data());
-        if (info) return info;
-      }
-      HIPCHK(hipStreamSynchronize(stream));  // (the staging buffer may still feed an earlier copy)
-      lbh::qn_pack_n(col, lbk::maxc_for(std::max(col, 1)), nm.data(), qn.h_n);
-      HIPCHK(hipMemcpyAsync(qn.d_n[md], qn.h_n, (size_t)QN_NP * sizeof(double), hipMemcpyHostToDevice, stream));
+      CHK(qn_upload_n(qn_coef_map(inv), qn.d_n[md]));
       qn.n_gen[md] = qn.gen;
     }
     CHK(qn_launched(lbk::launch_qn_diag<T>(q, n, Wc(), qn.head, col, qn.d_n[md], qn_alpha(inv), (T *)out_),
@@ -547,24 +605,14 @@
     std::vector<double> cf((size_t)d * k);
     for (int j = 0; j < k; ++j)
       std::copy_n(qn.eig_c[md].data() + (size_t)(which ? which[j] : j) * d, d, cf.data() + (size_t)j * d);
-    const lbk::WStore<T> w = Wc();
     T *out = (T *)out_;
     if (!qn.basis) {
       const T *any = ws + (int64_t)((qn.head - 1) % m) * ld;
-      for (int k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
-        const int kc = std::min(lbk::QN_KMAX, k - k0);
-        CHK(qn_expand_by(kc, cf.data() + (size_t)k0 * d, [&](const lbk::QnPiece &p, const double *coef) {
-          lbk::QnVecs<T> src{};
-          lbk::QnOuts<T> dst{};
-          for (int kk = 0; kk < p.k; ++kk) {
-            dst.p[kk] = out + (int64_t)(k0 + p.k0 + kk) * ldo;
-            src.p[kk] = p.c0 == 0 ? any : dst.p[kk];
-          }
-          return qn_launched(lbk::launch_qn_expand<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef,
-                                                      p.c0 == 0 ? 0.0 : 1.0, src, dst),
-                             "qn_expand");
-        }));
-      }
+      auto expand = [&](const QnPiece &p, const double *coef, QnVecs src, QnOuts dst) {
+        return qn_go("qn_expand", lbk::launch_qn_expand<T>, p, coef, p.c0 == 0 ? 0.0 : 1.0, src, dst);
+      };
+      for (int k0 = 0; k0 < k; k0 += lbk::QN_KMAX)
+        CHK(qn_expand_block(k0, lbk::qn_block_kc(k0, k), cf.data() + (size_t)k0 * d, any, 0, out, ldo, expand));
       return qn_finish();
     }
     const lbk::QnBasisPlan pl = lbk::qn_basis_plan(col, k);
@@ -585,8 +633,8 @@
       qn.coef_key = key;
     }
     for (const lbk::QnBasisTile &t : pl.tiles)
-      CHK(qn_launched(lbk::launch_qn_basis<T>(q, n, w, qn.head, col, t.c0, t.mc, t.acc,
-                                              qn.d_coef + t.off, k, out, ldo),
+      CHK(qn_launched(lbk::launch_qn_basis<T>(q, n, Wc(), qn.head, col, t.c0, t.mc, t.acc, qn.d_coef + t.off, k, out,
+                                              ldo),
                       "qn_basis"));
     return qn_finish();
   }
@@ -640,31 +688,11 @@
   // gw = [S, Y]' diag(w) [S, Y] over all rows (2col x 2col, the S block first): the weighted W'V pass with the
   // columns of W as its vectors, 4 at a time, then symmetrised as qn_model_mats does
   int qn_shift_gram(const double *wgt, double *gw) {
-    const int col = qn.col, d = 2 * col;
-    const lbk::WStore<T> w = Wc();
-    std::vector<double> sums((size_t)d * lbk::QN_KMAX);
-    for (int k0 = 0; k0 < d; k0 += lbk::QN_KMAX) {
-      const int kc = std::min(lbk::QN_KMAX, d - k0);
-      const T *v[lbk::QN_KMAX];
-      for (int kk = 0; kk < kc; ++kk) {
-        const int j = k0 + kk;
-        v[kk] = (j < col ? ws : wy) + (int64_t)((qn.head - 1 + (j < col ? j : j - col)) % m) * ld;
-      }
-      CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::None), sums.data(), nullptr, [&](const lbk::QnPiece &p) {
-        lbk::QnVecs<T> vv{};
-        for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v[p.k0 + kk];
-        return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, true, false, wgt,
-                                                       qn.d_part, qn.d_res + p.off),
-                           "qn_shift_wtv");
-      }));
-      for (int kk = 0; kk < kc; ++kk)
-        std::copy_n(sums.data() + (size_t)kk * d, d, gw + (size_t)(k0 + kk) * d);
-    }
-    for (int j = 0; j < d; ++j)
-      for (int i = 0; i < j; ++i) {
-        const double v = 0.5 * (gw[i + (size_t)j * d] + gw[j + (size_t)i * d]);
-        gw[i + (size_t)j * d] = gw[j + (size_t)i * d] = v;
-      }
+    const int d = 2 * qn.col;
+    CHK(qn_gram_by(0, d, [&](const QnPiece &p, QnVecs vv) {
+      return qn_go_sums("qn_shift_wtv", lbk::launch_qn_shift_wtv<T>, p, vv, true, false, wgt);
+    }, [&](int j, const double *sums) { std::copy_n(sums, d, gw + (size_t)j * d); }));
+    qn_symmetrise(d, gw);
     return 0;
   }
   int qn_shift_set(const void *d_, double mu, int64_t *h_pinned) override {
@@ -717,48 +745,34 @@
     CHK(qn_shift_live());
     return qn_shift_apply(false, k, v_, ldv, out_, ldo);
   }
+  // (cs; cy) of one vector from (S'(w o v); Y'(w o v)) by the factor of K: the map of which qn_shift_diag's N is the
+  // matrix
+  auto qn_shift_coef_map(const char *who) {
+    return [this, who](const double *stv, const double *ytv, double *cs, double *cy) {
+      if (lbh::qn_shift_coef(qn.col, qn.theta, qsh.kf.data(), stv, ytv, cs, cy))
+        return fail(LBFGSB_E_STATE, std::string(who) + ": a zero pivot in the factor of K");
+      return 0;
+    };
+  }
   // root: out_j = L v_j = sqrt(w) o v_j + w o (S cs_j + Y cy_j), (cs; cy) = C [S'(sqrt(w) o v_j); Y'(sqrt(w) o v_j)] --
   // the same two passes with the root's weights
   int qn_shift_apply(bool root, int64_t k, const void *v_, int64_t ldv, void *out_, int64_t ldo) {
     const int col = qn.col;
-    const lbk::WStore<T> w = Wc();
     const double *wgt = qsh.d_w[qsh.cur];
     const T *v = (const T *)v_;
-    T *out = (T *)out_;
-    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf(sums.size());
-    for (int64_t k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
-      const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
-      const T *vp[lbk::QN_KMAX];
-      for (int kk = 0; kk < kc; ++kk) vp[kk] = v + (k0 + kk) * ldv;
-      if (col > 0) {
-        CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::None), sums.data(), nullptr, [&](const lbk::QnPiece &p) {
-          lbk::QnVecs<T> vv{};
-          for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = vp[p.k0 + kk];
-          return qn_launched(lbk::launch_qn_shift_wtv<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, false, root, wgt,
-                                                         qn.d_part, qn.d_res + p.off),
-                             "qn_shift_wtv");
-        }));
-        for (int kk = 0; kk < kc; ++kk) {
-          const double *sv = sums.data() + (size_t)kk * 2 * col;
-          double *c = cf.data() + (size_t)kk * 2 * col;
-          if (root) qn_shift_root_map(1.0, sv, c);
-          else if (lbh::qn_shift_coef(col, qn.theta, qsh.kf.data(), sv, sv + col, c, c + col))
-            return fail(LBFGSB_E_STATE, "qn_shift_solve: a zero pivot in the factor of K");
-        }
-      }
-      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
-        lbk::QnVecs<T> src{};
-        lbk::QnOuts<T> dst{};
-        for (int kk = 0; kk < p.k; ++kk) {
-          dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
-          src.p[kk] = p.c0 == 0 ? vp[p.k0 + kk] : dst.p[kk];
-        }
-        return qn_launched(lbk::launch_qn_shift_expand<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef, src, wgt,
-                                                          p.c0 == 0, root, dst),
-                           "qn_shift_expand");
-      }));
-    }
-    return qn_finish();
+    return qn_blocks_by(
+        k, 0, QnCarry::None, v, ldv, (T *)out_, ldo,
+        [&](int64_t k0, const QnPiece &p) {
+          return qn_go_sums("qn_shift_wtv", lbk::launch_qn_shift_wtv<T>, p, qn_vecs(p, v, ldv, k0), false, root, wgt);
+        },
+        [&](int64_t, const double *sums, double, double *c) {
+          if (!root) return qn_shift_coef_map("qn_shift_solve")(sums, sums + col, c, c + col);
+          qn_root_map(qsh.root_c, 1.0, sums, c);
+          return 0;
+        },
+        [&](int64_t, const QnPiece &p, const double *coef, QnVecs src, QnOuts dst) {
+          return qn_go("qn_shift_expand", lbk::launch_qn_shift_expand<T>, p, coef, src, wgt, p.c0 == 0, root, dst);
+        });
   }
   // out_i = w_i + w_i^2 r_i' N r_i, N = K^-1 in the [S, Y] basis: the matrix of qn_shift_coef's map
   int qn_shift_diag(void *out_) override {
@@ -768,16 +782,7 @@
     if (col > lbk::MAXM) return fail(LBFGSB_E_ARG, "qn_shift_diag: more than 32 stored pairs");
     if (!qsh.d_n) HIPCHK(own.device(&qsh.d_n, (size_t)QN_NP * sizeof(double)));
     if (!qsh.n_ok) {
-      std::vector<double> nm((size_t)4 * col * col + 1);
-      if (col > 0) {
-        const int info = lbh::qn_nmat(col, [&](const double *stv, const double *ytv, double *cs, double *cy) {
-          return lbh::qn_shift_coef(col, qn.theta, qsh.kf.data(), stv, ytv, cs, cy);
-        }, nm.data());
-        if (info) return fail(LBFGSB_E_STATE, "qn_shift_diag: a zero pivot in the factor of K");
-      }
-      HIPCHK(hipStreamSynchronize(stream));  // (the staging buffer may still feed an earlier copy)
-      lbh::qn_pack_n(col, lbk::maxc_for(std::max(col, 1)), nm.data(), qn.h_n);
-      HIPCHK(hipMemcpyAsync(qsh.d_n, qn.h_n, (size_t)QN_NP * sizeof(double), hipMemcpyHostToDevice, stream));
+      CHK(qn_upload_n(qn_shift_coef_map("qn_shift_diag"), qsh.d_n));
       qsh.n_ok = true;
     }
     CHK(qn_launched(lbk::launch_qn_shift_diag<T>(q, n, Wc(), qn.head, col, qsh.d_n, qsh.d_w[qsh.cur], (T *)out_),
@@ -805,16 +810,6 @@
     qsh.root_logsum = logsum, qsh.root_gen = qsh.gen;
     return 0;
   }
-  // c = f C sums for one vector (sums = [S'(sqrt(w) o v); Y'(sqrt(w) o v)])
-  void qn_shift_root_map(double f, const double *sums, double *c) const {
-    const int d = 2 * qn.col;
-    const double *cm = qsh.root_c.data();
-    for (int i = 0; i < d; ++i) {
-      double t = 0.0;
-      for (int j = 0; j < d; ++j) t = t + cm[i + (size_t)j * d] * sums[j];
-      c[i] = f * t;
-    }
-  }
   // the free rows of all ranks, and nf log 2 pi + 2 nf log |scale| - log det (B + mu I + D) by the root's route (after
   // qn_shift_root_coef): -2 x the constant of a log-density under N(mean, scale^2 Sigma)
   double qn_shift_free() const { return (double)(nglob - qsh.pinned); }
@@ -835,72 +830,38 @@
                     double *h_logp) override {
     CHK(qn_ready());
     CHK(qn_shift_root_coef());
-    const int col = qn.col;
     const double lconst = h_logp ? qn_shift_log_norm(scale) : 0.0;
     const bool none_free = nglob == qsh.pinned;
-    double zz[lbk::QN_KMAX];
-    const lbk::WStore<T> w = Wc();
     const double *wgt = qsh.d_w[qsh.cur];
     const T *mean = (const T *)mean_;
-    T *out = (T *)out_;
-    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), cf(sums.size());
-    for (int64_t k0 = 0; k0 < k;) {
-      const int64_t s0 = first + k0;
-      const int kc = (s0 & 1) ? 1 : (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
-      if (col > 0 || h_logp) {
-        CHK(qn_sums_by(lbk::qn_plan(col, kc, h_logp ? QnCarry::Norms : QnCarry::None), sums.data(), zz,
-                       [&](const lbk::QnPiece &p) {
-          return qn_launched(lbk::launch_qn_shift_wtz<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, seed, row0,
-                                                         s0 + p.k0, p.carry == QnCarry::Norms, wgt, qn.d_part,
-                                                         qn.d_res + p.off),
-                             "qn_shift_wtz");
-        }));
-        for (int kk = 0; kk < kc && col > 0; ++kk)
-          qn_shift_root_map(scale, sums.data() + (size_t)kk * 2 * col, cf.data() + (size_t)kk * 2 * col);
-        for (int kk = 0; kk < kc && h_logp; ++kk) h_logp[k0 + kk] = none_free ? 0.0 : -0.5 * (lconst + zz[kk]);
-      }
-      CHK(qn_expand_by(kc, cf.data(), [&](const lbk::QnPiece &p, const double *coef) {
-        lbk::QnOuts<T> dst{};
-        for (int kk = 0; kk < p.k; ++kk) dst.p[kk] = out + (k0 + p.k0 + kk) * ldo;
-        return qn_launched(lbk::launch_qn_shift_draw<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, coef, scale, seed, row0,
-                                                        s0 + p.k0, p.c0 == 0, mean, wgt, dst),
-                           "qn_shift_draw");
-      }));
-      k0 += kc;
-    }
-    return qn_finish();
+    return qn_blocks_by(
+        k, first, h_logp ? QnCarry::Norms : QnCarry::None, nullptr, 0, (T *)out_, ldo,
+        [&](int64_t k0, const QnPiece &p) {
+          return qn_go_sums("qn_shift_wtz", lbk::launch_qn_shift_wtz<T>, p, seed, row0, first + k0 + p.k0,
+                            p.carry == QnCarry::Norms, wgt);
+        },
+        [&](int64_t j, const double *sums, double zz, double *c) {
+          qn_root_map(qsh.root_c, scale, sums, c);
+          if (h_logp) h_logp[j] = none_free ? 0.0 : -0.5 * (lconst + zz);
+          return 0;
+        },
+        [&](int64_t k0, const QnPiece &p, const double *coef, QnVecs, QnOuts dst) {
+          return qn_go("qn_shift_draw", lbk::launch_qn_shift_draw<T>, p, coef, scale, seed, row0, first + k0 + p.k0,
+                       p.c0 == 0, mean, wgt, dst);
+        });
   }
   // q_j = (v_j - center)'(B + mu I + D)(v_j - center) on the free rows = sum Delta_i q_i^2 + t'N_B t with
   // t = [S, Y]'(f o q): qn_quad's route for B with the Delta-weighted squared norm in place of theta q'q, one pass and
   // nothing written
   int qn_shift_quad_by(int64_t k, const T *v, int64_t ldv, const T *center, double *h_q) {
-    const int col = qn.col;
-    if (col > 0 && qn.theta_gram) CHK(qn_gram());
-    const std::vector<double> dg = qn_dg();
-    const lbk::WStore<T> w = Wc();
     const double *wgt = qsh.d_w[qsh.cur];
-    std::vector<double> sums((size_t)2 * std::max(col, 1) * lbk::QN_KMAX), c((size_t)2 * std::max(col, 1));
-    double dd[lbk::QN_KMAX];
-    for (int64_t k0 = 0; k0 < k; k0 += lbk::QN_KMAX) {
-      const int kc = (int)std::min<int64_t>(lbk::QN_KMAX, k - k0);
-      CHK(qn_sums_by(lbk::qn_plan(col, kc, QnCarry::Norms), sums.data(), dd, [&](const lbk::QnPiece &p) {
-        lbk::QnVecs<T> vv{};
-        for (int kk = 0; kk < p.k; ++kk) vv.p[kk] = v + (k0 + p.k0 + kk) * ldv;
-        return qn_launched(lbk::launch_qn_shift_wtd<T>(q, n, w, qn.head, col, p.c0, p.mc, p.k, vv, center,
-                                                       p.carry == QnCarry::Norms, wgt, qn.d_part, qn.d_res + p.off),
-                           "qn_shift_wtd");
-      }));
-      for (int kk = 0; kk < kc; ++kk) {
-        const double *sv = sums.data() + (size_t)kk * 2 * col;
-        double t = 0.0;  // t'(N_B t), S part then Y part, ascending
-        if (col > 0) {
-          CHK(qn_coef(false, dg.data(), sv, sv + col, c.data(), c.data() + col));
-          for (int i = 0; i < 2 * col; ++i) t = t + sv[i] * c[(size_t)i];
-        }
-        h_q[k0 + kk] = dd[kk] + t;
-      }
-    }
-    return 0;
+    return qn_quad_sums(
+        false, k, h_q,
+        [&](int64_t k0, const QnPiece &p) {
+          return qn_go_sums("qn_shift_wtd", lbk::launch_qn_shift_wtd<T>, p, qn_vecs(p, v, ldv, k0), center,
+                            p.carry == QnCarry::Norms, wgt);
+        },
+        [](double dd) { return dd; });
   }
   int qn_shift_quad(int64_t k, const void *v, int64_t ldv, const void *center, double *h_q) override {
     CHK(qn_ready());

@@ -1,6 +1,7 @@
 // qn_plan_check.cpp -- the tiling plan of the curvature-model operators (lbfgsb_amd/csrc/qn_plan.hpp) against a naive
 // restatement of its rule, for every col in 0 .. 70 and 1024, every block of 1 .. QN_KMAX vectors, the three carries
-// and the expansion variant.  Built and run under AddressSanitizer + UndefinedBehaviorSanitizer by
+// and the expansion variant; and the split of a call's k = 1 .. 9 vectors or samples into blocks (qn_block_kc), from
+// an even and from an odd first sample.  Built and run under AddressSanitizer + UndefinedBehaviorSanitizer by
 // tests/test_qn_plan_cpu.py; every buffer a scatter or a pack touches is a heap block of exactly its size.
 //
 // The restatement does not use qn_mc / qn_kmax / qn_piece_k: it walks (column, vector) pairs and says in which slot
@@ -147,6 +148,33 @@ static void check_one(int col, int kc, QnCarry carry, bool expand) {
   for (int u : used) CHECK(u == 1);
 }
 
+// The blocks of a call on k vectors (qn_block_kc) against the rule said naively: loaded vectors go four at a time, the
+// rest last; samples from `first` go as an odd first sample alone, then four at a time from an even one, the rest last.
+// Returns the number of blocks walked.
+static int check_blocks(int k, int first, bool samples) {
+  g_col = -1, g_kc = k, g_carry = first, g_expand = samples;  // (the report's fields, reused)
+  std::vector<int> want;                                       // the widths, naively
+  int left = k;
+  if (samples && first % 2 != 0) want.push_back(1), left -= 1;
+  for (; left >= 4; left -= 4) want.push_back(4);
+  if (left > 0) want.push_back(left);
+  size_t nb = 0;
+  std::vector<int> seen((size_t)k, 0);
+  for (int64_t k0 = 0; k0 < k; ++nb) {
+    const int64_t s0 = samples ? first + k0 : 0;
+    const int kc = qn_block_kc(k0, k, s0);
+    CHECK(nb < want.size() && kc == want[nb < want.size() ? nb : 0]);
+    CHECK(kc >= 1 && kc <= QN_KMAX && k0 + kc <= k);
+    CHECK(kc == 1 || s0 % 2 == 0);  // (a block of more than one sample: whole pairs)
+    if (kc < 1) break;
+    for (int kk = 0; kk < kc && k0 + kk < k; ++kk) seen[(size_t)(k0 + kk)]++;
+    k0 += kc;
+  }
+  CHECK(nb == want.size());
+  for (int c : seen) CHECK(c == 1);
+  return (int)nb;
+}
+
 int main() {
   static_assert(qn_mc(1) == 5 && qn_mc(5) == 5 && qn_mc(6) == 10 && qn_mc(10) == 10 && qn_mc(11) == 16, "capacities");
   static_assert(qn_res(MAX_M) == 2 * (MAX_M + 16) * 4 + 10, "the result buffer");
@@ -158,6 +186,13 @@ int main() {
       check_one(col, kc, QnCarry::None, true), ++cases;
     }
   }
+  // the blocks of a call: k = 1 .. 9 loaded vectors, and k = 1 .. 9 samples from an even and from an odd first sample
+  int blocks = 0;
+  for (int k = 1; k <= 9; ++k) {
+    blocks += check_blocks(k, 0, false);
+    for (int first : {0, 6, 1, 7}) blocks += check_blocks(k, first, true);
+  }
+  std::printf("qn_plan_check: %d blocks of vectors walked\n", blocks);
   std::printf("qn_plan_check: %d cases, %d failed\n", cases, failures);
   return failures ? 1 : 0;
 }

@@ -4,6 +4,7 @@ flight -- one spilled register cost the fp32 m = 20 update pass 3.17 -> 4.68 ms 
 the code objects embedded in the built library (profiles/scripts/kernel_resources.py: the AMDHSA metadata
 note of every kernel); runs on the CPU, right after the build.  The only kernels allowed a private segment
 are rocPRIM's radix-sort kernels (library code behind the first iteration's full breakpoint sort)."""
+import csv
 import importlib.util
 import os
 
@@ -30,6 +31,37 @@ def test_no_kernel_of_the_library_uses_scratch():
                                                                 "wtv_kernel<"))]
     assert len(hot) > 100
     assert all(r["vgpr"] <= 512 for r in hot)
+
+
+def _qn_table():
+    """profiles/qn_kernel_resources.csv: the kernels of the curvature-model operators (k_qn*.hip) as the build before
+    their passes were moved onto shared helpers had them (kernel_resources.py --csv on its six objects)"""
+    with open(os.path.join(ROOT, "profiles", "qn_kernel_resources.csv"), newline="") as f:
+        return {r["kernel"]: r for r in csv.DictReader(f)}
+
+
+def test_the_curvature_model_kernels_are_the_recorded_set():
+    """no qn_* instantiation appears or disappears without the table saying so"""
+    kr, rows = _resources()
+    built = {kr.short(r["kernel"]) for r in rows if kr.short(r["kernel"]).startswith("qn_")}
+    table = set(_qn_table())
+    assert len(table) > 1900
+    assert built == table, (sorted(built - table)[:5], sorted(table - built)[:5])
+
+
+def test_the_curvature_model_kernels_keep_their_occupancy():
+    """against the table: no qn_* kernel at fewer waves per SIMD, none with scratch, none with more LDS"""
+    kr, rows = _resources()
+    table = _qn_table()
+    bad = []
+    for r in rows:
+        name = kr.short(r["kernel"])
+        if name in table:
+            t = table[name]
+            if r["waves_per_simd"] < int(t["waves_per_simd"]) or r["scratch"] != 0 or r["lds"] > int(t["lds_bytes"]):
+                bad.append((name, r["vgpr"], int(t["vgpr"]), r["waves_per_simd"], int(t["waves_per_simd"]),
+                            r["scratch"], r["lds"]))
+    assert not bad, "(kernel, vgpr now, then, waves now, then, scratch, lds): %s" % bad[:10]
 
 
 def test_hot_kernels_of_the_headline_config_keep_their_occupancy():
