@@ -21,7 +21,7 @@ po.build(ref=False)
 world, first, count = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 comm = sys.argv[4] if len(sys.argv) > 4 else "fakerccl"
 if comm == "fakerccl":
-    os.environ["LBFGSB_RCCL_LIBRARY"] = tm._fake_rccl()
+    os.environ["LBFGSB_RCCL_LIBRARY"] = tm.fake_rccl()
 KINDS = [("make", 200), ("linear", 200), ("lattice", 300), ("rosenchain", 300), ("scaled", 100)]
 t0 = time.time()
 worst = 0

@@ -6,8 +6,8 @@ cd $R
 python - <<'PY'
 import sys
 sys.path.insert(0, "tests")
-import test_gpu_multirank as tm
-print(tm._fake_rccl())
+import _sharded
+print(_sharded.fake_rccl())
 PY
 FAKE=$R/tests/_build/libfake_rccl.so
 LBFGSB_BENCH_SHARE_GPU=1 LBFGSB_RCCL_LIBRARY=$FAKE MASTER_ADDR=127.0.0.1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \

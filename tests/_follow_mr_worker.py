@@ -5,13 +5,11 @@ Runs the separable quadratic with all four bound types and edits bounds during t
 owns, and on the last rank only a new u pointer -- and writes the rows of every NEW_X return, the task sequence
 and this rank's x to out_prefix.<rank>.npz.
 usage: _follow_mr_worker.py rank world port mode n m iters out_prefix"""
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _mr_common import join, leave, quadratic_rows
 
 
 def run(rank, world, port, mode, n, m, iters, out_prefix):
@@ -19,26 +17,8 @@ def run(rank, world, port, mode, n, m, iters, out_prefix):
     import lbfgsb_amd
     from oracle import pyoracle as po
 
-    if mode != "single":
-        import torch.distributed as dist
-        dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    row0, n_loc = lbfgsb_amd.block_partition(n, world, rank)
-    sol = lbfgsb_amd.DeviceSolver(n_loc, m, n_global=n, row0=row0, device=0, follow_bounds=True)
-    if mode == "gloo":
-        lbfgsb_amd.attach_host_group(sol, rank, world)
-    elif mode == "fakerccl":
-        ids = [lbfgsb_amd.DeviceSolver.rccl_unique_id() if rank == 0 else None]
-        dist.broadcast_object_list(ids, 0)
-        sol.init_rccl(ids[0], rank, world)
-    p = po.problem_quadratic(n, m, mixed_nbd=True)
-    sl = slice(row0, row0 + n_loc)
-    x = torch.from_numpy(p.x0[sl].copy()).to(dev)
-    g = torch.zeros_like(x)
-    l = torch.from_numpy(p.l[sl].copy()).to(dev)
-    u = torch.from_numpy(p.u[sl].copy()).to(dev)
-    nbd = torch.from_numpy(p.nbd[sl].astype(np.int32)).to(dev)
+    sol, row0, n_loc, dev = join(rank, world, port, mode, n, m, follow_bounds=True)
+    x, g, l, u, nbd = quadratic_rows(po, n, m, row0, n_loc, dev)
     last0 = lbfgsb_amd.block_partition(n, 3, 2)[0]   # (rows of the last rank of a 3-way split: one owner at 2 and 3)
 
     def edit_rows(arr, lo, hi, value):               # global rows [lo, hi) that this rank owns
@@ -70,12 +50,8 @@ def run(rank, world, port, mode, n, m, iters, out_prefix):
                 break
         else:
             break
-    np.savez(out_prefix + ".%d.npz" % rank, rows=np.array(rows, np.float64), tasks=np.array(tasks),
-             x=x.cpu().numpy(), stats=np.array(sol.bounds_stats()), row0=row0)
-    sol.close()
-    if mode != "single":
-        dist.barrier()
-        dist.destroy_process_group()
+    leave(sol, rank, out_prefix, dict(rows=np.array(rows, np.float64), tasks=np.array(tasks), x=x.cpu().numpy(),
+                                      stats=np.array(sol.bounds_stats()), row0=row0), state=False)
 
 
 if __name__ == "__main__":

@@ -4,35 +4,20 @@ a gloo host group ('gloo') or the library's communicator code path with the shar
 collectively on this rank's rows (no run is needed) and the ordered list per rank, and writes the summary, this
 rank's per-row outputs and its lists to out_prefix.<rank>.npz.
 usage: _kkt_mr_worker.py rank world port mode case.npz tol out_prefix"""
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _mr_common import join, leave
+
 MASKS = (0b01100, 0b00011, 0b10000, 31)
 
 
 def run(rank, world, port, mode, case, tol, out_prefix):
     import torch
-    import torch.distributed as dist
-    import lbfgsb_amd
 
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
     data = np.load(case)
-    n = data["x"].size
-    row0, n_loc = lbfgsb_amd.block_partition(n, world, rank)
-    sol = lbfgsb_amd.DeviceSolver(n_loc, 3, n_global=n, row0=row0, device=0)
-    if mode == "gloo":
-        lbfgsb_amd.attach_host_group(sol, rank, world)
-    else:
-        ids = [lbfgsb_amd.DeviceSolver.rccl_unique_id() if rank == 0 else None]
-        dist.broadcast_object_list(ids, 0)
-        sol.init_rccl(ids[0], rank, world)
-        assert "libfake_rccl" in open("/proc/self/maps").read()   # (the stand-in, not the real library)
+    sol, row0, n_loc, dev = join(rank, world, port, mode, data["x"].size, 3)
     sl = slice(row0, row0 + n_loc)
     x, l, u, nbd, g = (torch.from_numpy(data[k][sl].copy()).to(dev) for k in ("x", "l", "u", "nbd", "g"))
     rep = sol.kkt(x, l, u, nbd, g, tol=tol)
@@ -41,10 +26,7 @@ def run(rank, world, port, mode, case, tol, out_prefix):
     for mask in MASKS:
         codes = [c for c in range(-1, 4) if mask >> (c + 1) & 1]
         res["idx%d" % mask] = sol.kkt_indices(rep.status, codes).cpu().numpy()
-    np.savez(out_prefix + ".%d.npz" % rank, **res)
-    sol.close()
-    dist.barrier()
-    dist.destroy_process_group()
+    leave(sol, rank, out_prefix, res, state=False)
 
 
 if __name__ == "__main__":

@@ -22,12 +22,8 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
     import torch.distributed as dist
     import lbfgsb_amd
     from oracle import pyoracle as po
+    from _mr_common import attach, join, upload
 
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank,
-                            world_size=world)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    row0, n_loc = lbfgsb_amd.block_partition(n, world, rank)
     options = {}
     if variant == "symx":
         options["exact_always"] = 1
@@ -38,30 +34,14 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
     if os.environ.get("LBFGSB_TEST_SPEC_CAPTURE") == "1":
         options["spec_capture"] = 1      # the update pass hands the next walk's breakpoints over (tests/test_gpu_handover.py)
 
-    def make_solver():
-        s_ = lbfgsb_amd.DeviceSolver(n_loc, m, n_global=n, row0=row0, device=0,
-                                     parallel_gcp=(variant in ("pgcp", "pgcp2")),
-                                     # LBFGSB_F_DEFER_LNSRCH over several ranks (the deferred sums are one more
-                                     # reduced segment of every rank's fetch): tests/test_gpu_multirank.py
-                                     defer_lnsrch=os.environ.get("LBFGSB_TEST_DEFER") == "1",
-                                     # (this worker evaluates f, g with sol.objective: the solver's own stream)
-                                     same_stream_objective=os.environ.get("LBFGSB_TEST_DEFER") == "1",
-                                     index_ties=(variant == "sym"),
-                                     options=options or None)
-        if mode == "gloo":
-            lbfgsb_amd.attach_host_group(s_, rank, world)
-        elif mode == "rccl1":
-            assert world == 1
-            lbfgsb_amd.attach_rccl(s_, 0, 1, dev)
-        elif mode == "fakerccl":
-            # the library's communicator code path (ncclAllReduce / ncclAllGather on the solver's
-            # stream) with several ranks on ONE GPU: LBFGSB_RCCL_LIBRARY points at tests/fake_rccl.cpp
-            ids = [lbfgsb_amd.DeviceSolver.rccl_unique_id() if rank == 0 else None]
-            dist.broadcast_object_list(ids, 0)
-            s_.init_rccl(ids[0], rank, world)
-            assert "libfake_rccl" in open("/proc/self/maps").read()   # (not the real library)
-        return s_
-    sol = make_solver()
+    kwargs = dict(parallel_gcp=(variant in ("pgcp", "pgcp2")),
+                  # LBFGSB_F_DEFER_LNSRCH over several ranks (the deferred sums are one more reduced segment of every
+                  # rank's fetch): tests/test_gpu_multirank.py
+                  defer_lnsrch=os.environ.get("LBFGSB_TEST_DEFER") == "1",
+                  # (this worker evaluates f, g with sol.objective: the solver's own stream)
+                  same_stream_objective=os.environ.get("LBFGSB_TEST_DEFER") == "1",
+                  index_ties=(variant == "sym"), options=options or None)
+    sol, row0, n_loc, dev = join(rank, world, port, mode, n, m, **kwargs)
     two_scale = None
     if variant == "pgcp2":
         p, two_scale = two_scale_problem(po, n, m)
@@ -69,7 +49,6 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
         p, two_scale = symmetric_problem(po, n, m)
     elif variant == "stair":
         # the staircase case of tests/_handover_cases.py with this n and world: every rank's last n_loc % 128 rows bounded
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
         import _handover_cases as hc
         case, = [c for c in hc.CASES if (c.n, c.m, c.world) == (n, m, world)]
         p, two_scale = case.problem(po)
@@ -78,12 +57,7 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
     else:
         p = po.problem_quadratic(n, m, mixed_nbd=(variant == "1"))
     kind = 1 if variant == "rosen" else 0
-    sl = slice(row0, row0 + n_loc)
-    x = torch.from_numpy(p.x0[sl].copy()).to(dev)
-    g = torch.zeros_like(x)
-    l = torch.from_numpy(p.l[sl].copy()).to(dev)
-    u = torch.from_numpy(p.u[sl].copy()).to(dev)
-    nbd = torch.from_numpy(p.nbd[sl].astype(np.int32)).to(dev)
+    x, g, l, u, nbd = upload(p, row0, n_loc, dev)
     rows = []
     stopcpu = None
     for _ in range(100000):
@@ -129,7 +103,8 @@ def run(rank, world, port, mode, n, m, iters, variant, out_path):
                          sol.dsave.copy(), sol.f.copy())
                 sol.close()
                 dist.barrier()
-                sol = make_solver()
+                sol = lbfgsb_amd.DeviceSolver(n_loc, m, n_global=n, row0=row0, device=0, **kwargs)
+                attach(sol, rank, world, mode)
                 sol.import_state(wa, iwa, saved[3])
                 sol.task[:], sol.csave[:], sol.lsave[:] = saved[0], saved[1], saved[2]
                 sol.isave[:], sol.dsave[:], sol.f[:] = saved[3], saved[4], saved[5]
@@ -270,7 +245,7 @@ def run_fuzz(rank, world, port, first, count, iters, out_path, family=None, scal
     import torch.distributed as dist
     import lbfgsb_amd
     from oracle import pyoracle as po
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _mr_common import attach, upload
     import test_gpu_fuzz as tf
     from test_gpu_fuzz import _explain_divergence
 
@@ -293,19 +268,9 @@ def run_fuzz(rank, world, port, first, count, iters, out_path, family=None, scal
             po.run(po.Engine("oracle"), p, max_iter=iters, snapshot=lambda k, s: ro.append(row(s.task_s, s.isave, s.f[0])))
         row0, n_loc = lbfgsb_amd.block_partition(p.n, world, rank)
         sol = lbfgsb_amd.DeviceSolver(n_loc, p.m, n_global=p.n, row0=row0, device=0)
-        if comm == "fakerccl":
-            ids = [lbfgsb_amd.DeviceSolver.rccl_unique_id() if rank == 0 else None]
-            dist.broadcast_object_list(ids, 0)
-            sol.init_rccl(ids[0], rank, world)
-            assert "libfake_rccl" in open("/proc/self/maps").read()
-        else:
-            lbfgsb_amd.attach_host_group(sol, rank, world)
+        attach(sol, rank, world, comm)
         sl = slice(row0, row0 + n_loc)
-        x = torch.from_numpy(p.x0[sl].copy()).to(dev)
-        g = torch.zeros_like(x)
-        l = torch.from_numpy(p.l[sl].copy()).to(dev)
-        u = torch.from_numpy(p.u[sl].copy()).to(dev)
-        nbd = torch.from_numpy(p.nbd[sl].astype(np.int32)).to(dev)
+        x, g, l, u, nbd = upload(p, row0, n_loc, dev)
         rows, prev, split, verdict = [], None, None, None
         for k in range(100000):
             t = sol.setulb(x, l, u, nbd, g, 0.0, 0.0)

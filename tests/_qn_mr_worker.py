@@ -4,49 +4,22 @@ a gloo host group ('gloo') or the library's communicator code path with the shar
 then calls the curvature-model operator collectively (B V, H V for 3 vectors, diag(B), diag(H)) and writes this
 rank's rows of the results, of the exported Ws / Wy and the model's scalars to out_prefix.<rank>.npz.
 usage: _qn_mr_worker.py rank world port mode n m iters out_prefix"""
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _mr_common import join, leave, quadratic_rows, run_to
 
 
 def run(rank, world, port, mode, n, m, iters, out_prefix):
     import torch
-    import torch.distributed as dist
-    import lbfgsb_amd
     from oracle import pyoracle as po
 
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
-    row0, n_loc = lbfgsb_amd.block_partition(n, world, rank)
-    sol = lbfgsb_amd.DeviceSolver(n_loc, m, n_global=n, row0=row0, device=0)
-    if mode == "gloo":
-        lbfgsb_amd.attach_host_group(sol, rank, world)
-    else:
-        ids = [lbfgsb_amd.DeviceSolver.rccl_unique_id() if rank == 0 else None]
-        dist.broadcast_object_list(ids, 0)
-        sol.init_rccl(ids[0], rank, world)
-        assert "libfake_rccl" in open("/proc/self/maps").read()   # (the stand-in, not the real library)
-    p = po.problem_quadratic(n, m, mixed_nbd=True)
-    sl = slice(row0, row0 + n_loc)
-    x = torch.from_numpy(p.x0[sl].copy()).to(dev)
-    g = torch.zeros_like(x)
-    l = torch.from_numpy(p.l[sl].copy()).to(dev)
-    u = torch.from_numpy(p.u[sl].copy()).to(dev)
-    nbd = torch.from_numpy(p.nbd[sl].astype(np.int32)).to(dev)
-    for _ in range(100000):
-        t = sol.setulb(x, l, u, nbd, g, 0.0, 0.0)
-        if t.startswith("FG"):
-            sol.f[0] = sol.objective(0, x, g)
-        elif not t.startswith("NEW_X") or sol.isave[29] >= iters:
-            break
-    assert t.startswith("NEW_X"), t
+    sol, row0, n_loc, dev = join(rank, world, port, mode, n, m)
+    x, g, l, u, nbd = quadratic_rows(po, n, m, row0, n_loc, dev)
+    run_to(sol, x, l, u, nbd, g, iters)
     V = np.random.default_rng(17).standard_normal((3, n))          # the same global vectors on every rank
-    vt = torch.from_numpy(V[:, sl].copy()).to(dev)
+    vt = torch.from_numpy(V[:, row0:row0 + n_loc].copy()).to(dev)
     res = dict(bv=sol.qn_apply(vt).cpu().numpy(), hv=sol.qn_apply(vt, inverse=True).cpu().numpy(),
                h1=sol.qn_apply(vt[1].contiguous(), inverse=True).cpu().numpy())
     col = int(sol.isave[27])
@@ -55,10 +28,7 @@ def run(rank, world, port, mode, n, m, iters, out_prefix):
     wa, _ = sol.export_state()
     res.update(ws=wa[:m * n_loc].reshape(m, n_loc), wy=wa[m * n_loc:2 * m * n_loc].reshape(m, n_loc),
                head=int(sol.isave[26]), col=col, theta=float(sol.dsave[0]), row0=row0, V=V)
-    np.savez(out_prefix + ".%d.npz" % rank, **res)
-    sol.close()
-    dist.barrier()
-    dist.destroy_process_group()
+    leave(sol, rank, out_prefix, res, state=False)
 
 
 if __name__ == "__main__":

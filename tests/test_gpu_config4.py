@@ -25,7 +25,7 @@ ROOT = os.path.dirname(HERE)
 
 def test_config4_eight_ranks_full_size_on_one_gpu(oracle_built, tmp_path):
     import torch
-    from test_gpu_multirank import _fake_rccl
+    from _sharded import fake_rccl
     free_b, _tot = torch.cuda.mem_get_info()
     if free_b < 60 * (1 << 30):
         pytest.skip("needs ~40 GB of HBM")
@@ -35,7 +35,7 @@ def test_config4_eight_ranks_full_size_on_one_gpu(oracle_built, tmp_path):
     #  a device-wide synchronising runtime call of one rank thread would otherwise wait for the stream-side
     #  waits of the other ranks; the asynchronous form is what the multi-PROCESS tests of
     #  test_gpu_multirank.py run on, the count / datatype check acts in both)
-    env = dict(os.environ, LBFGSB_RCCL_LIBRARY=_fake_rccl(), LBFGSB_FAKE_RCCL_SYNC="1")
+    env = dict(os.environ, LBFGSB_RCCL_LIBRARY=fake_rccl(), LBFGSB_FAKE_RCCL_SYNC="1")
     rc = subprocess.call([sys.executable, os.path.join(HERE, "_c4_worker.py"), str(world), str(n), str(m),
                           str(iters), out], env=env, timeout=900)
     res = json.load(open(out))

@@ -95,8 +95,8 @@ def scenario_mismatch():
 def _child(name):
     """the two ranks are two child processes: each has hardware queues of its own, so a rank's stream-side wait
     never sits in front of the other rank's copies (ranks that are threads of one process can share a queue)"""
-    from test_gpu_multirank import _fake_rccl
-    so = _fake_rccl()
+    from _sharded import fake_rccl
+    so = fake_rccl()
     uid = UniqueId()
     assert _lib_at(so).ncclGetUniqueId(C.byref(uid)) == 0
     env = dict(os.environ, LBFGSB_FAKE_RCCL_SO=so)

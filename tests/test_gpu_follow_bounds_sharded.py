@@ -3,35 +3,24 @@ or the library's communicator path with the shared-memory RCCL stand-in (tests/f
 test_gpu_qn_sharded.py.  Edits touch rows of one rank only, and one rank alone passes a new u pointer: every rank
 must rebuild at the same entry (the changed-row count is reduced over the ranks), see the same task sequence,
 and the rows must equal the single-rank run of the same edits."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from test_gpu_qn_sharded import _free_port, _fake_rccl
+from _sharded import fake_rccl, launch_workers
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 N, M, ITERS = 3001, 6, 14
 
 
 def _run(tmp_path, tag, world, mode):
-    port = _free_port()
-    prefix = str(tmp_path / tag)
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_follow_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(N), str(M), str(ITERS), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    return [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+    return launch_workers("_follow_mr_worker.py", world, mode, N, M, ITERS, prefix=str(tmp_path / tag))
 
 
 @pytest.mark.parametrize("world,mode", [(2, "gloo"), (3, "gloo"), (2, "fakerccl"), (3, "fakerccl")])
 def test_sharded_edits_rebuild_on_every_rank_together(oracle_built, tmp_path, monkeypatch, world, mode):
     one = _run(tmp_path, "single", 1, "single")[0]
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     parts = _run(tmp_path, "mr", world, mode)
     for pt in parts:
         assert list(pt["tasks"]) == list(one["tasks"])

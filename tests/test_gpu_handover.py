@@ -151,16 +151,17 @@ def test_handover_changes_no_return_of_an_undisturbed_run(env, label, layout, ca
 def test_sharded_handover(oracle_built, tmp_path, monkeypatch, world, mode, name, layout, floor):
     """every rank bounds ITS last n_loc % 128 rows; the walk is replicated, so every rank must count the same served
     walks, and the rows are the single-rank oracle's (as tests/test_gpu_multirank.py demands of a sharded run)"""
-    from test_gpu_multirank import _fake_rccl, launch
+    from _sharded import fake_rccl, launch_workers
     po = oracle_built
     case = hc.BY_NAME[name]
     assert case.world == world
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     if layout:
         monkeypatch.setenv("LBFGSB_TEST_COMPACT", "1")
     monkeypatch.setenv("LBFGSB_TEST_SPEC_CAPTURE", "1")
-    res = launch(world, mode, case.n, case.m, hc.ITERS, "stair", str(tmp_path / "out.json"))
+    res = launch_workers("_mr_worker.py", world, mode, case.n, case.m, hc.ITERS, "stair",
+                         prefix=str(tmp_path / "out.json"))
     p, _ = case.problem(po)
     rows = []
     s = po.run(po.Engine("oracle"), p, max_iter=hc.ITERS,

@@ -3,36 +3,14 @@
 Every rank calls lbfgsb_hip_kkt collectively with its own rows: the summary is identical on every rank and equals
 the single-rank one bit for bit; the per-rank outputs and lists, concatenated in rank order, equal the single-rank
 ones; the indices are global."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from _sharded import fake_rccl, launch_workers
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 MASKS = (0b01100, 0b00011, 0b10000, 31)
 TOL = float(np.float32(1e-3))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _fake_rccl():
-    so = os.path.join(HERE, "_build", "libfake_rccl.so")
-    src = os.path.join(HERE, "fake_rccl.cpp")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17",
-                               "-fPIC", "-shared", src, "-o", so, "-lrt", "-lpthread"])
-    return so
 
 
 def _case(n, seed):
@@ -70,17 +48,11 @@ def test_sharded_report_equals_single_rank(oracle_built, tmp_path, monkeypatch, 
     import torch
     import lbfgsb_amd as la
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     case = _case(n, 40 + n)
     np.savez(str(tmp_path / "case.npz"), **case)
-    port = _free_port()
-    prefix = str(tmp_path / "kkt")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_kkt_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(tmp_path / "case.npz"), repr(TOL), prefix])
-             for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+    parts = launch_workers("_kkt_mr_worker.py", world, mode, tmp_path / "case.npz", repr(TOL),
+                           prefix=str(tmp_path / "kkt"))
     # the single-rank report of the same arrays
     sol = la.DeviceSolver(n, 3)
     try:

@@ -4,34 +4,21 @@ communicator of ONE rank, which drives ncclAllReduce/ncclAllGather on the solver
 Both must reproduce the single-rank oracle trajectory: integers exactly, f to 1e-9."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from _sharded import fake_rccl, launch_workers
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def launch(world, mode, n, m, iters, mixed, out):
-    port = free_port()
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(n), str(m), str(iters),
-                               mixed if isinstance(mixed, str) else ("1" if mixed else "0"), out])
-             for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    return json.load(open(out))
+    return launch_workers("_mr_worker.py", world, mode, n, m, iters,
+                          mixed if isinstance(mixed, str) else ("1" if mixed else "0"), prefix=out)
 
 
 def oracle_rows(po, n, m, iters, mixed):
@@ -68,7 +55,7 @@ def oracle_rows(po, n, m, iters, mixed):
 def test_sharded_trajectory_matches_oracle(oracle_built, tmp_path, monkeypatch, world, mode, n, m, iters, mixed):
     po = oracle_built
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     res = launch(world, mode, n, m, iters, mixed, str(tmp_path / "out.json"))
     rows, x = oracle_rows(po, n, m, iters, mixed)
     assert len(res["rows"]) == len(rows) == iters
@@ -128,7 +115,7 @@ def test_sharded_parallel_gcp_with_pairs_stored(oracle_built, tmp_path, monkeypa
     spec.loader.exec_module(wk)
     n, m, iters = 200_000, 5, 8
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     res = launch(world, mode, n, m, iters, "pgcp2", str(tmp_path / "out.json"))
     p, _ = wk.two_scale_problem(po, n, m)
     rows = []
@@ -160,7 +147,7 @@ def test_sharded_exact_tie_order(oracle_built, tmp_path, monkeypatch, world, mod
     spec.loader.exec_module(wk)
     n, m, iters = 257 * 8, 5, 40
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     p, _ = wk.symmetric_problem(po, n, m)
     rows = []
     so = po.run(po.Engine("oracle"), p, max_iter=iters,
@@ -197,7 +184,7 @@ def test_sharded_checkpoint_and_resume(oracle_built, tmp_path, monkeypatch, worl
     po = oracle_built
     n, m, iters = 40_009, 6, 14
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     res = launch(world, mode, n, m, iters, "ckpt", str(tmp_path / "out.json"))
     rows, x = oracle_rows(po, n, m, iters, False)
     assert len(res["rows"]) == len(rows) == iters
@@ -229,18 +216,6 @@ def test_sharded_random_problems_match_oracle(oracle_built, tmp_path, world, fir
     assert splits <= 0.2 * count, splits   # (a sanity bound on how often drift shows, not an allowance)
 
 
-def _fake_rccl():
-    """Build tests/fake_rccl.cpp (shared-memory stand-in for the RCCL entry points) on demand."""
-    so = os.path.join(HERE, "_build", "libfake_rccl.so")
-    src = os.path.join(HERE, "fake_rccl.cpp")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        # (compiled as HIP: the stand-in launches one tiny kernel -- the stream-side wait of a collective)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17",
-                               "-fPIC", "-shared", src, "-o", so, "-lrt", "-lpthread"])
-    return so
-
-
 @pytest.mark.parametrize("world,n,m,iters,mixed", [
     (2, 20011, 7, 8, True),
     (3, 300000, 10, 3, False),     # long first walk: all-gathered record chunks, merged on every rank
@@ -256,7 +231,7 @@ def test_communicator_code_path_with_several_ranks(oracle_built, tmp_path, monke
     library at a shared-memory stand-in for those seven entry points; everything above them is
     the production code.  Same trajectory as the single-rank oracle."""
     po = oracle_built
-    monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+    monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     res = launch(world, "fakerccl", n, m, iters, mixed, str(tmp_path / "out.json"))
     rows, x = oracle_rows(po, n, m, iters, mixed)
     assert len(res["rows"]) == len(rows) == iters
@@ -276,7 +251,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     the very route the driver's own `python -m torch.distributed.run ... bench.py --gpus N` takes.  The scaling keys
     asserted here (collective_us, the roofline, bench_detail.json) are measured by a --full run."""
     root = os.path.dirname(HERE)
-    env = dict(os.environ, LBFGSB_BENCH_SHARE_GPU="1", LBFGSB_RCCL_LIBRARY=_fake_rccl(),
+    env = dict(os.environ, LBFGSB_BENCH_SHARE_GPU="1", LBFGSB_RCCL_LIBRARY=fake_rccl(),
                MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
@@ -316,7 +291,7 @@ def test_deferred_line_search_sums_over_several_ranks(oracle_built, tmp_path, mo
     the oracle's trajectory."""
     po = oracle_built
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     base = launch(world, mode, n, m, iters, mixed, str(tmp_path / "base.json"))
     monkeypatch.setenv("LBFGSB_TEST_DEFER", "1")
     res = launch(world, mode, n, m, iters, mixed, str(tmp_path / "defer.json"))
@@ -341,7 +316,7 @@ def test_stop_cpu_sharded(oracle_built, tmp_path, monkeypatch, world, mode, defe
     po = oracle_built
     n, m, iters = 20011, 7, 9
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     if defer:
         monkeypatch.setenv("LBFGSB_TEST_DEFER", "1")
     res = launch(world, mode, n, m, iters, "stopcpu", str(tmp_path / "out.json"))
@@ -363,7 +338,7 @@ def test_sharded_runs_on_the_compact_layout(oracle_built, tmp_path, monkeypatch,
     po = oracle_built
     n, m, iters = 20011, 7, 12
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
     monkeypatch.setenv("LBFGSB_TEST_COMPACT", "1")
     res = launch(world, mode, n, m, iters, variant, str(tmp_path / "out.json"))
     rows, x = oracle_rows(po, n, m, iters, variant is True)

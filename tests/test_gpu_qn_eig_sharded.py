@@ -3,42 +3,28 @@ host group, n = 4099 split unevenly.  The eigenvalues are the same bits on both 
 the single-rank checks of tests/test_gpu_qn_eig.py against ONE context that imported the concatenated state
 (orthonormal, A U = U Lambda and A^-1 U = U / Lambda through its qn_apply, within _check_root's bounds), and their
 signs agree with that context's own vectors."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from _sharded import import_glued, launch_workers
 from test_gpu_qn_eig import SEP, _orth_bound
 from test_gpu_qn_root import _cond_and_norm, _model
-from test_gpu_qn_root_sharded import _free_port, _glue
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def test_sharded_spectrum_and_vectors(oracle_built, tmp_path):
     import torch
     import lbfgsb_amd as la
     n, m, iters, world = 4099, 7, 10, 2
-    port = _free_port()
-    prefix = str(tmp_path / "qneig")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_qn_eig_mr_worker.py"), str(r), str(world),
-                               str(port), str(n), str(m), str(iters), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+    parts = launch_workers("_qn_eig_mr_worker.py", world, n, m, iters, prefix=str(tmp_path / "qneig"))
     assert len({int(p["n_loc"]) for p in parts}) > 1                       # an uneven split
     assert int(parts[0]["col"]) == m and int(parts[0]["head"]) > 1          # a full ring whose head has wrapped
     for key in ("bulk_b", "bulk_h", "lam_b", "lam_h"):
         assert parts[0][key].tobytes() == parts[1][key].tobytes(), key     # the same bits on every rank
     one = la.DeviceSolver(n, m)
     try:
-        isave = parts[0]["isave"]
-        wa = _glue(parts, n, m)
-        one.import_state(wa, np.zeros(3 * n, np.int32), isave)
-        one.isave[:] = isave
+        wa = import_glued(one, parts, n, m)
         one.dsave[0] = float(parts[0]["theta"])  # (what _model reads)
         B, col, theta, W = _model(one, wa)
         cond, nb = _cond_and_norm(B, theta, W)

@@ -4,26 +4,20 @@ unevenly, m = 17 (two column tiles, pieces of at most 2 vectors), k = 5 (pieces 
 Every rank gets the same bits, and every entry is within 1e-12 |d_a|_A |d_b|_A of ONE context's that imported the
 concatenated state."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from _sharded import fake_rccl, import_glued, launch_workers, one_context
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-sys.path.insert(0, HERE)
-try:
-    from test_gpu_qn_root_sharded import _fake_rccl, _free_port, _glue
-finally:
-    sys.path.pop(0)
 
 
 @pytest.mark.parametrize("world,mode,iters", [(2, "gloo", 21), (3, "fakerccl", 20)])
 def test_sharded_gram(oracle_built, tmp_path, monkeypatch, world, mode, iters):
     import torch
-    import lbfgsb_amd as la
     sys.path.insert(0, HERE)
     try:
         import _qn_gram_mr_worker as wk
@@ -31,14 +25,8 @@ def test_sharded_gram(oracle_built, tmp_path, monkeypatch, world, mode, iters):
         sys.path.remove(HERE)
     n, m = 1000, 17
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
-    port = _free_port()
-    prefix = str(tmp_path / "qngram")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_qn_gram_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(n), str(m), str(iters), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
+    parts = launch_workers("_qn_gram_mr_worker.py", world, mode, n, m, iters, prefix=str(tmp_path / "qngram"))
     assert len({int(p["n_loc"]) for p in parts}) == world                # an uneven split
     assert [int(p["row0"]) for p in parts] == [wk.cut(n, world, r)[0] for r in range(world)]
     assert len({(int(p["col"]), int(p["head"])) for p in parts}) == 1
@@ -59,18 +47,9 @@ def test_sharded_gram(oracle_built, tmp_path, monkeypatch, world, mode, iters):
         print("%s: max |sharded - one rank| / (1e-12 |d_a|_A |d_b|_A) = %.3e" % (name, (err / tol).max()))
         assert np.all(err <= tol), name
 
-    one = la.DeviceSolver(n, m)
-    try:
-        x = torch.zeros(n, dtype=torch.float64, device="cuda")
-        g = torch.zeros_like(x)
-        nbd = torch.zeros(n, dtype=torch.int32, device="cuda")
-        assert one.setulb(x, x.clone(), x.clone(), nbd, g, 0.0, 0.0).startswith("FG_START")
+    with one_context(n, m) as one:
         close("g0", got["g0"], one.qn_gram(V, center=cen))
-        isave = got["isave"]
-        one.import_state(_glue(parts, n, m), np.zeros(3 * n, np.int32), isave)
-        one.isave[:] = isave
+        import_glued(one, parts, n, m)
         close("gb", got["gb"], one.qn_gram(V, center=cen))
         close("gh", got["gh"], one.qn_gram(V, center=cen, inverse=True))
         close("gn", got["gn"], one.qn_gram(V, inverse=True))
-    finally:
-        one.close()

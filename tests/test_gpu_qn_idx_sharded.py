@@ -5,20 +5,15 @@ are the same bytes on every rank; the rows of the pairs equal exactly those of O
 concatenated state, the blocks are within 1e-12 (relative to the largest entry) of that context's, and the
 concatenated columns within 1e-12 in the relative 2-norm."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from _sharded import fake_rccl, import_glued, launch_workers, one_context
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-sys.path.insert(0, HERE)
-try:
-    from test_gpu_qn_root_sharded import _fake_rccl, _free_port, _glue
-finally:
-    sys.path.pop(0)
 
 HOST = ("rows", "b_sq", "b_rect", "h_sq", "h_rect", "s_sq", "s_rect")
 
@@ -26,7 +21,6 @@ HOST = ("rows", "b_sq", "b_rect", "h_sq", "h_rect", "s_sq", "s_rect")
 @pytest.mark.parametrize("world,mode,iters", [(2, "gloo", 14), (3, "fakerccl", 13)])
 def test_sharded_idx(oracle_built, tmp_path, monkeypatch, world, mode, iters):
     import torch
-    import lbfgsb_amd as la
     sys.path.insert(0, HERE)
     try:
         import _qn_idx_mr_worker as wk
@@ -34,14 +28,8 @@ def test_sharded_idx(oracle_built, tmp_path, monkeypatch, world, mode, iters):
         sys.path.remove(HERE)
     n, m = 4099, 10
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
-    port = _free_port()
-    prefix = str(tmp_path / "qnidx")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_qn_idx_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(n), str(m), str(iters), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
+    parts = launch_workers("_qn_idx_mr_worker.py", world, mode, n, m, iters, prefix=str(tmp_path / "qnidx"))
     assert len({int(p["n_loc"]) for p in parts}) == world                # an uneven split
     assert len({(int(p["col"]), int(p["head"])) for p in parts}) == 1
     assert int(parts[0]["col"]) == m
@@ -53,23 +41,14 @@ def test_sharded_idx(oracle_built, tmp_path, monkeypatch, world, mode, iters):
         assert len({p[key].tobytes() for p in parts}) == 1, key           # the same bytes on every rank
 
     d = torch.from_numpy(wk.shift(n, world)).cuda()
-    one = la.DeviceSolver(n, m)
-    try:
-        x = torch.zeros(n, dtype=torch.float64, device="cuda")
-        g = torch.zeros_like(x)
-        nbd = torch.zeros(n, dtype=torch.int32, device="cuda")
-        assert one.setulb(x, x.clone(), x.clone(), nbd, g, 0.0, 0.0).startswith("FG_START")
-        isave = parts[0]["isave"]
-        one.import_state(_glue(parts, n, m), np.zeros(3 * n, np.int32), isave)
-        one.isave[:] = isave
+    with one_context(n, m) as one:
+        import_glued(one, parts, n, m)
         sh = one.qn_shift(d, wk.MU)
         ref = dict(rows=one.qn_rows(ia), s_sq=sh.block(ia), s_rect=sh.block(ia, ib),
                    s_cols=sh.columns(ia).cpu().numpy())
         for inv, tag in ((False, "b"), (True, "h")):
             ref[tag + "_sq"], ref[tag + "_rect"] = one.qn_block(ia, inverse=inv), one.qn_block(ia, ib, inverse=inv)
             ref[tag + "_cols"] = one.qn_cols(ia, inverse=inv).cpu().numpy()
-    finally:
-        one.close()
     got = parts[0]
     assert got["rows"].shape == (len(ia), 2 * m) and np.array_equal(got["rows"], ref["rows"])   # exactly
     assert np.abs(got["rows"]).max() > 0.0

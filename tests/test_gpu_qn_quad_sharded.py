@@ -4,21 +4,16 @@ tests/fake_rccl.cpp), n = 4099 split unevenly, m = 10.  Every rank gets the same
 relative of ONE context's that imported the concatenated state; z'z of a draw does not depend on the sharding to that
 bound, and the concatenated draws equal the single context's (bit for bit while no pair is stored)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from _sharded import fake_rccl, import_glued, launch_workers, one_context
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 LOG2PI = float(np.log(2.0 * np.pi))
-
-sys.path.insert(0, HERE)
-try:
-    from test_gpu_qn_root_sharded import _fake_rccl, _free_port, _glue
-finally:
-    sys.path.pop(0)
 
 
 def _zz(lp, n, scale, logdet):
@@ -28,7 +23,6 @@ def _zz(lp, n, scale, logdet):
 @pytest.mark.parametrize("world,mode,iters", [(2, "gloo", 14), (3, "fakerccl", 13)])
 def test_sharded_quad_and_logpdf(oracle_built, tmp_path, monkeypatch, world, mode, iters):
     import torch
-    import lbfgsb_amd as la
     sys.path.insert(0, HERE)
     try:
         import _qn_quad_mr_worker as wk
@@ -36,14 +30,8 @@ def test_sharded_quad_and_logpdf(oracle_built, tmp_path, monkeypatch, world, mod
         sys.path.remove(HERE)
     n, m = 4099, 10
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
-    port = _free_port()
-    prefix = str(tmp_path / "qnquad")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_qn_quad_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(n), str(m), str(iters), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
+    parts = launch_workers("_qn_quad_mr_worker.py", world, mode, n, m, iters, prefix=str(tmp_path / "qnquad"))
     assert len({int(p["n_loc"]) for p in parts}) > 1                       # an uneven split
     assert len({(int(p["col"]), int(p["head"])) for p in parts}) == 1
     assert int(parts[0]["col"]) == m and int(parts[0]["head"]) > 1          # a full ring whose head has wrapped
@@ -61,19 +49,12 @@ def test_sharded_quad_and_logpdf(oracle_built, tmp_path, monkeypatch, world, mod
         print("%s: |sharded - one rank| / |one rank| = %.3e" % (name, err))
         assert np.all(np.abs(a - b) <= 1e-10 * np.abs(b)), name
 
-    one = la.DeviceSolver(n, m)
-    try:
-        x = torch.zeros(n, dtype=torch.float64, device="cuda")
-        g = torch.zeros_like(x)
-        nbd = torch.zeros(n, dtype=torch.int32, device="cuda")
-        assert one.setulb(x, x.clone(), x.clone(), nbd, g, 0.0, 0.0).startswith("FG_START")
+    with one_context(n, m) as one:
         d0, lp0 = one.qn_draw(wk.K, wk.SEED, first=wk.FIRST, mean=mean, scale=wk.SCALE, return_logpdf=True)
         assert np.array_equal(np.concatenate([p["d0"] for p in parts], axis=1), d0.cpu().numpy())
         close("q0", got["q0"], one.qn_quad(V, center=mean))
         close("z'z, no pair", _zz(got["lp0"], n, wk.SCALE, 0.0), _zz(lp0, n, wk.SCALE, 0.0))
-        isave = got["isave"]
-        one.import_state(_glue(parts, n, m), np.zeros(3 * n, np.int32), isave)
-        one.isave[:] = isave
+        import_glued(one, parts, n, m)
         close("qb", got["qb"], one.qn_quad(V, center=mean))
         close("qh", got["qh"], one.qn_quad(V, center=mean, inverse=True))
         close("lpb", got["lpb"], one.qn_logpdf(V, mean=mean, scale=wk.SCALE, inverse=False))
@@ -89,5 +70,3 @@ def test_sharded_quad_and_logpdf(oracle_built, tmp_path, monkeypatch, world, mod
             close(lk, got[lk], lp)
             close("z'z of " + dk, _zz(got[lk], n, wk.SCALE, float(got[ldk])),
                   _zz(lp, n, wk.SCALE, one.qn_logdet(inverse=inverse)))
-    finally:
-        one.close()

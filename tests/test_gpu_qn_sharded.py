@@ -2,34 +2,12 @@
 host group (host reducer) or the library's communicator path with the shared-memory RCCL stand-in
 (tests/fake_rccl.cpp).  Every rank calls collectively with its own rows; the concatenated outputs must equal the
 dense numpy model built from the concatenated per-rank exports (theta I updated by the pairs in ring order)."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from _sharded import fake_rccl, launch_workers
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _fake_rccl():
-    so = os.path.join(HERE, "_build", "libfake_rccl.so")
-    src = os.path.join(HERE, "fake_rccl.cpp")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17",
-                               "-fPIC", "-shared", src, "-o", so, "-lrt", "-lpthread"])
-    return so
 
 
 @pytest.mark.parametrize("world,mode,n,m,iters", [
@@ -40,14 +18,8 @@ def _fake_rccl():
 ])
 def test_sharded_operator_matches_dense_model(oracle_built, tmp_path, monkeypatch, world, mode, n, m, iters):
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
-    port = _free_port()
-    prefix = str(tmp_path / "qn")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_qn_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(n), str(m), str(iters), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
+    parts = launch_workers("_qn_mr_worker.py", world, mode, n, m, iters, prefix=str(tmp_path / "qn"))
     assert len({(int(p["col"]), int(p["head"]), float(p["theta"])) for p in parts}) == 1
     col, head, theta = int(parts[0]["col"]), int(parts[0]["head"]), float(parts[0]["theta"])
     assert col == m and head > 1                     # a full ring whose head has wrapped

@@ -1,42 +1,30 @@
 """Draws and densities of the model plus a diagonal on a sharded context: two rank processes on one GPU through the
 host reducer (a gloo group), n = 4099 split unevenly, m = 10, every third row pinned and a run of 40 pinned rows across
-the rank boundary (the shift of tests/_qn_shift_mr_worker.py).  The log-densities, the quadratic forms and the pinned
+the rank boundary (the shift of tests/_mr_common.py).  The log-densities, the quadratic forms and the pinned
 count are the same bits on both ranks; the concatenated draws and factor products are within 1e-13 (relative, in the
 2-norm) of ONE context's that imported the concatenated state -- a draw is a function of (seed, global row, sample),
 not of the sharding -- and the host numbers within 1e-12 relative of that context's."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from _sharded import import_glued, launch_workers, one_context
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-sys.path.insert(0, HERE)
-try:
-    from test_gpu_qn_root_sharded import _free_port, _glue
-finally:
-    sys.path.pop(0)
 
 
 def test_sharded_shift_draws(oracle_built, tmp_path):
     import torch
-    import lbfgsb_amd as la
     sys.path.insert(0, HERE)
     try:
         import _qn_shift_draw_mr_worker as wk
     finally:
         sys.path.remove(HERE)
     n, m, world, iters = 4099, 10, 2, 14
-    port = _free_port()
-    prefix = str(tmp_path / "qnshiftdraw")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_qn_shift_draw_mr_worker.py"), str(r), str(world),
-                               str(port), str(n), str(m), str(iters), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+    parts = launch_workers("_qn_shift_draw_mr_worker.py", world, n, m, iters, prefix=str(tmp_path / "qnshiftdraw"))
     assert len({int(p["n_loc"]) for p in parts}) == world                # an uneven split
     assert len({(int(p["col"]), int(p["head"])) for p in parts}) == 1 and int(parts[0]["col"]) == m
     d = wk.shift(n, world)
@@ -66,16 +54,7 @@ def test_sharded_shift_draws(oracle_built, tmp_path):
             assert np.all(err <= 1e-12)
         assert int(ref["pinned"]) == int(parts[0][tag + "_pinned"])
 
-    one = la.DeviceSolver(n, m)
-    try:
-        x = torch.zeros(n, dtype=torch.float64, device="cuda")
-        g = torch.zeros_like(x)
-        nbd = torch.zeros(n, dtype=torch.int32, device="cuda")
-        assert one.setulb(x, x.clone(), x.clone(), nbd, g, 0.0, 0.0).startswith("FG_START")
+    with one_context(n, m) as one:
         close("s0", one.qn_shift(dt, wk.MU))
-        isave = parts[0]["isave"]
-        one.import_state(_glue(parts, n, m), np.zeros(3 * n, np.int32), isave)
-        one.isave[:] = isave
+        import_glued(one, parts, n, m)
         close("s1", one.qn_shift(dt, wk.MU))
-    finally:
-        one.close()

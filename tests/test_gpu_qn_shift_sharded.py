@@ -4,26 +4,20 @@ m = 10, every third row pinned and a run of 40 pinned rows across every rank bou
 are the same bits on every rank, and the concatenated solves and diagonals are within 1e-12 (relative, in the 2-norm)
 of ONE context's that imported the concatenated state."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from _sharded import fake_rccl, import_glued, launch_workers, one_context
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-sys.path.insert(0, HERE)
-try:
-    from test_gpu_qn_root_sharded import _fake_rccl, _free_port, _glue
-finally:
-    sys.path.pop(0)
 
 
 @pytest.mark.parametrize("world,mode,iters", [(2, "gloo", 14), (3, "fakerccl", 13)])
 def test_sharded_shift(oracle_built, tmp_path, monkeypatch, world, mode, iters):
     import torch
-    import lbfgsb_amd as la
     sys.path.insert(0, HERE)
     try:
         import _qn_shift_mr_worker as wk
@@ -31,14 +25,8 @@ def test_sharded_shift(oracle_built, tmp_path, monkeypatch, world, mode, iters):
         sys.path.remove(HERE)
     n, m = 4099, 10
     if mode == "fakerccl":
-        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", _fake_rccl())
-    port = _free_port()
-    prefix = str(tmp_path / "qnshift")
-    procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "_qn_shift_mr_worker.py"), str(r), str(world),
-                               str(port), mode, str(n), str(m), str(iters), prefix]) for r in range(world)]
-    rcs = [p.wait(timeout=300) for p in procs]
-    assert rcs == [0] * world, rcs
-    parts = [np.load(prefix + ".%d.npz" % r) for r in range(world)]
+        monkeypatch.setenv("LBFGSB_RCCL_LIBRARY", fake_rccl())
+    parts = launch_workers("_qn_shift_mr_worker.py", world, mode, n, m, iters, prefix=str(tmp_path / "qnshift"))
     assert len({int(p["n_loc"]) for p in parts}) == world                # an uneven split
     assert len({(int(p["col"]), int(p["head"])) for p in parts}) == 1
     assert int(parts[0]["col"]) == m
@@ -67,16 +55,7 @@ def test_sharded_shift(oracle_built, tmp_path, monkeypatch, world, mode, iters):
         assert np.all(x[:, np.isinf(d)] == 0.0) and np.all(dg[np.isinf(d)] == 0.0)
         assert sh.pinned == int(parts[0][tag + "_pinned"])
 
-    one = la.DeviceSolver(n, m)
-    try:
-        x = torch.zeros(n, dtype=torch.float64, device="cuda")
-        g = torch.zeros_like(x)
-        nbd = torch.zeros(n, dtype=torch.int32, device="cuda")
-        assert one.setulb(x, x.clone(), x.clone(), nbd, g, 0.0, 0.0).startswith("FG_START")
+    with one_context(n, m) as one:
         close("s0", one.qn_shift(dt, wk.MU))
-        isave = parts[0]["isave"]
-        one.import_state(_glue(parts, n, m), np.zeros(3 * n, np.int32), isave)
-        one.isave[:] = isave
+        import_glued(one, parts, n, m)
         close("s1", one.qn_shift(dt, wk.MU))
-    finally:
-        one.close()
