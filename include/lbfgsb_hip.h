@@ -569,6 +569,36 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  * write device memory follow qn_eigvec.  LBFGSB_E_ARG, nothing changed: a NULL pointer, k < 1, k over the cap, an ld
  * that is too small, an index outside 0 .. n_global - 1, a mode that is not B or H.  When, REAL32 (W and out fp32,
  * every sum and host result fp64) and the refusals are qn_apply's, and the run does not notice the calls.
+ *
+ * Pairs in and out: a curvature model of the caller's own.  The stored pairs (s_j, y_j) and theta are all that the
+ * entries above read; these three move them as DEVICE data, with no run required and nothing of the reference's wa
+ * through host memory.  S, Y, s, y are device memory of the context's real kind: pair j (oldest first, as qn_rows
+ * orders its columns) at S + j*lds and Y + j*ldy, n_local rows each, lds, ldy >= n_local, element alignment only.  On
+ * several ranks the calls are collective: every rank passes its rows, the sums are reduced as qn_apply's, the host
+ * results have the same bits on every rank.  Streams as qn_apply, LBFGSB_F_NO_RETURN_SYNC included for the device
+ * outputs of qn_pairs_get.
+ *   qn_pairs_get: valid exactly when qn_apply is.  *h_col = the number of stored pairs, *h_theta = theta, then the
+ *     pairs in ring order from the oldest into S and Y.  cap = 0 (S, Y may be NULL) is the counting call; 0 < cap <
+ *     *h_col is LBFGSB_E_ARG with *h_col and *h_theta written.  W is read in the layout it is in (2col*16 B per row in
+ *     fp64); the run does not notice the call.
+ *   qn_pairs_set: loads 0 <= k <= m pairs.  theta > 0 and finite is taken as given; theta = 0 means y'y / s'y of the
+ *     newest pair (k >= 1), as matupd sets it; anything else is LBFGSB_E_ARG.  Allowed on a context that has never
+ *     run, and at any return: it ENDS the run and puts the context into model mode -- the pairs sit in the ring slots
+ *     1 .. k in natural row order, nothing deferred or pending survives, and sy, ss, wt (formt) and the Gram cache of
+ *     the operators are made from one Gram pass over the loaded columns, so the first operator call afterwards runs
+ *     none.  k = 0 is the empty model B = theta I.  LBFGSB_E_ARG when some s_j'y_j is not finite or not positive
+ *     (the message names the pair) or when formt fails: the context then holds NO model and NO run -- every qn entry
+ *     returns LBFGSB_E_STATE until the next qn_pairs_set, START or import_state.
+ *   qn_pairs_push: model mode only (LBFGSB_E_STATE otherwise, nothing changed: the pairs of a run belong to the run).
+ *     One pass over W reads s, y and the stored columns and carries S's, S'y, Y's, Y'y, s's, s'y, y'y, in fp64 also in
+ *     REAL32 contexts ((2col + 2)*8 B per row in fp64, nothing written).  The pair is stored iff s'y is finite and
+ *     s'y > epsmch sqrt(s's y'y), epsmch of the context's real kind.  *h_stored = 0: not stored, nothing changed.
+ *     *h_stored = 1: the two columns are written (32 B per row), a full ring drops its oldest pair, and sy, ss, theta
+ *     (= y'y / s'y unless the argument is > 0), wt and the Gram cache follow on the host from the sums alone as matupd
+ *     and formt do it -- no further pass over W, none at the next qn_apply either.  *h_stored = -1: formt failed and
+ *     the model was refreshed as the reference refreshes (no pair, theta = 1); the return is still 0.
+ * In model mode lbfgsb_hip_setulb_dev / _dev_pp (and the host forms above them) return LBFGSB_E_STATE for every task
+ * but START; START and lbfgsb_hip_import_state leave the mode.
  * ------------------------------------------------------------------------- */
 #define LBFGSB_QN_B 0
 #define LBFGSB_QN_H 1
@@ -615,6 +645,11 @@ int lbfgsb_hip_qn_cols(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int64_t *
 int lbfgsb_hip_qn_shift_block(lbfgsb_hip_ctx *ctx, int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib,
                               double *h_a, int64_t lda);
 int lbfgsb_hip_qn_shift_cols(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_idx, void *out, int64_t ldo);
+int lbfgsb_hip_qn_pairs_get(lbfgsb_hip_ctx *ctx, int32_t cap, int32_t *h_col, double *h_theta, void *S, int64_t lds,
+                            void *Y, int64_t ldy);
+int lbfgsb_hip_qn_pairs_set(lbfgsb_hip_ctx *ctx, int32_t k, const void *S, int64_t lds, const void *Y, int64_t ldy,
+                            double theta);
+int lbfgsb_hip_qn_pairs_push(lbfgsb_hip_ctx *ctx, const void *s, const void *y, double theta, int32_t *h_stored);
 
 /* -------------------------------------------------------------------------
  * The active set, the bound multipliers and the projected gradient as device data.

@@ -77,6 +77,10 @@ PROTOTYPES = {
     "lbfgsb_hip_qn_shift_block": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64),
                                             C.POINTER(C.c_double), C.c_int64]),
     "lbfgsb_hip_qn_shift_cols": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), _vp, C.c_int64]),
+    "lbfgsb_hip_qn_pairs_get": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), _vp, C.c_int64,
+                                          _vp, C.c_int64]),
+    "lbfgsb_hip_qn_pairs_set": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64, C.c_double]),
+    "lbfgsb_hip_qn_pairs_push": (C.c_int, [_vp, _vp, _vp, C.c_double, C.POINTER(C.c_int32)]),
     "lbfgsb_hip_qn_shift_sqrt": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
     "lbfgsb_hip_qn_shift_draw": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int64, _vp, C.c_double, _vp, C.c_int64]),
     "lbfgsb_hip_qn_shift_draw_logpdf": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int64, _vp, C.c_double, _vp,

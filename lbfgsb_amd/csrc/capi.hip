@@ -392,6 +392,31 @@ int lbfgsb_hip_qn_shift_cols(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_id
   if (k < 1 || k > 128 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_shift_cols: k < 1, k > 128 or ldo < n_local");
   return ctx->qn_shift_cols(k, h_idx, out, ldo);
 }
+int lbfgsb_hip_qn_pairs_get(lbfgsb_hip_ctx *ctx, int32_t cap, int32_t *h_col, double *h_theta, void *S, int64_t lds,
+                            void *Y, int64_t ldy) {
+  if (!ctx || !h_col || !h_theta) return fail(LBFGSB_E_ARG, "qn_pairs_get: NULL argument");
+  if (cap < 0) return fail(LBFGSB_E_ARG, "qn_pairs_get: cap < 0");
+  if (cap > 0 && (!S || !Y)) return fail(LBFGSB_E_ARG, "qn_pairs_get: NULL S or Y with cap > 0");
+  if (cap > 0 && (lds < ctx->n || ldy < ctx->n)) return fail(LBFGSB_E_ARG, "qn_pairs_get: ld < n_local");
+  return ctx->qn_pairs_get(cap, h_col, h_theta, S, lds, Y, ldy);
+}
+int lbfgsb_hip_qn_pairs_set(lbfgsb_hip_ctx *ctx, int32_t k, const void *S, int64_t lds, const void *Y, int64_t ldy,
+                            double theta) {
+  if (!ctx) return fail(LBFGSB_E_ARG, "qn_pairs_set: NULL argument");
+  if (k < 0 || k > ctx->m) return fail(LBFGSB_E_ARG, "qn_pairs_set: k outside 0 .. m");
+  if (k > 0 && (!S || !Y)) return fail(LBFGSB_E_ARG, "qn_pairs_set: NULL S or Y with k > 0");
+  if (k > 0 && (lds < ctx->n || ldy < ctx->n)) return fail(LBFGSB_E_ARG, "qn_pairs_set: ld < n_local");
+  if (!(theta >= 0.0) || !std::isfinite(theta))
+    return fail(LBFGSB_E_ARG, "qn_pairs_set: theta must be > 0 and finite, or 0 (y'y / s'y of the newest pair)");
+  if (theta == 0.0 && k < 1) return fail(LBFGSB_E_ARG, "qn_pairs_set: theta = 0 (from the newest pair) needs k >= 1");
+  return ctx->qn_pairs_set(k, S, lds, Y, ldy, theta);
+}
+int lbfgsb_hip_qn_pairs_push(lbfgsb_hip_ctx *ctx, const void *s, const void *y, double theta, int32_t *h_stored) {
+  if (!ctx || !s || !y || !h_stored) return fail(LBFGSB_E_ARG, "qn_pairs_push: NULL argument");
+  if (!(theta >= 0.0) || !std::isfinite(theta))
+    return fail(LBFGSB_E_ARG, "qn_pairs_push: theta must be > 0 and finite, or 0 (y'y / s'y of the pair)");
+  return ctx->qn_pairs_push(s, y, theta, h_stored);
+}
 
 int lbfgsb_hip_kkt(lbfgsb_hip_ctx *ctx, const void *x, const void *l, const void *u, const int32_t *nbd,
                    const void *g, double tol, void *pg_out, void *mult_out, int8_t *status_out, int64_t *h_cnt,

@@ -721,6 +721,82 @@ inline int qn_eig(int d, double alpha, double cut, int64_t rmax, const double *g
   return 0;
 }
 
+// ---- a curvature model of the caller's own (lbfgsb_hip_qn_pairs_set / _push, solver_qn_pairs.inl) ----
+// The m x m matrices the operators read, from the Grams of col loaded pairs (col x col, column-major, logical order:
+// sts[i + j col] = s_i's_j, sty[i + j col] = s_i'y_j, yty likewise): sy = the lower triangle and diagonal of S'Y, ss =
+// the upper triangle of S'S as matupd keeps them (reference src/lbfgsb.f90:2311-2340), theta = theta_in when that is
+// > 0, else y'y / s'y of the newest pair (:2318; needs col >= 1), then wt by formt (:1926-1963).  Returns 0; j + 1
+// when s_j'y_j is not finite or not positive (no pair is stored without s'y > 0, :820-826); -1 for theta_in = 0
+// without a pair; -3 when formt fails.  sy, ss and wt are written in every case.
+inline int qn_pairs_factor(int m, int col, const double *sts, const double *sty, const double *yty, double theta_in,
+                           double *sy_, double *ss_, double *wt_, double *theta) {
+  Mat sy{sy_, m}, ss{ss_, m};
+  for (int j = 0; j < col; ++j)
+    for (int i = 0; i < col; ++i) {
+      if (i >= j) sy(i, j) = sty[i + (size_t)j * col];
+      if (i <= j) ss(i, j) = sts[i + (size_t)j * col];
+    }
+  for (int j = 0; j < col; ++j)
+    if (!std::isfinite(sy(j, j)) || !(sy(j, j) > 0.0)) return j + 1;
+  if (theta_in > 0.0) {
+    *theta = theta_in;
+  } else {
+    if (col < 1) return -1;
+    *theta = yty[(size_t)(col - 1) * (col + 1)] / sy(col - 1, col - 1);
+  }
+  return formt(m, wt_, sy_, ss_, col, *theta);
+}
+
+// matupd's host part for one appended pair (s, y) (reference src/lbfgsb.f90:2303-2340), from the sums alone: the
+// pointer update (:2303-2309; a full ring drops the oldest pair), the shift of Ss and Sy once the memory is full
+// (:2324-2330), Sy's new row s'y_j and Ss's new column s_j's over the pairs that stay, oldest first (:2333-2338),
+// the two diagonal entries (:2339-2344), theta = y'y / s'y (:2318) unless theta_in > 0, then formt (:849).  s_old,
+// y_old: s_j's and y_j's for the col pairs stored BEFORE the call, oldest first.  Returns formt's info.
+inline int qn_pairs_append(int m, int &col, int &head, int &itail, double *sy_, double *ss_, double *wt_,
+                           double &theta, const double *s_old, const double *y_old, double sts, double sty, double yty,
+                           double theta_in) {
+  Mat sy{sy_, m}, ss{ss_, m};
+  const bool full = col == m;
+  if (!full) {
+    col = col + 1;
+    itail = (head + col - 2) % m + 1;
+  } else {
+    itail = itail % m + 1;
+    head = head % m + 1;
+  }
+  theta = theta_in > 0.0 ? theta_in : yty / sty;
+  if (full)
+    for (int j = 0; j < col - 1; ++j) {
+      for (int i = 0; i <= j; ++i) ss(i, j) = ss(i + 1, j + 1);
+      for (int i = j; i < col - 1; ++i) sy(i, j) = sy(i + 1, j + 1);
+    }
+  const int drop = full ? 1 : 0;  // (the sums against the pair that leaves are not used)
+  for (int j = 0; j < col - 1; ++j) {
+    sy(col - 1, j) = y_old[j + drop];
+    ss(j, col - 1) = s_old[j + drop];
+  }
+  ss(col - 1, col - 1) = sts;
+  sy(col - 1, col - 1) = sty;
+  return formt(m, wt_, sy_, ss_, col, theta);
+}
+
+// The same step on a full Gram g (colold x colold, column-major, logical order) of the operators' cache: the oldest
+// pair's row and column leave when the ring was full, then the new pair's column cnew[i] = (pair i)'(new), its row
+// rnew[i] = (new)'(pair i) and the diagonal entry, for the colold pairs stored before, oldest first.
+inline void qn_gram_append(int m, int colold, std::vector<double> &g, const double *cnew, const double *rnew,
+                           double diag) {
+  const int drop = colold == m ? 1 : 0, keep = colold - drop, col = keep + 1;
+  std::vector<double> o((size_t)col * col, 0.0);
+  for (int j = 0; j < keep; ++j)
+    for (int i = 0; i < keep; ++i) o[i + (size_t)j * col] = g[(i + drop) + (size_t)(j + drop) * colold];
+  for (int i = 0; i < keep; ++i) {
+    o[i + (size_t)keep * col] = cnew[i + drop];
+    o[keep + (size_t)i * col] = rnew[i + drop];
+  }
+  o[(size_t)keep * (col + 1)] = diag;
+  g.swap(o);
+}
+
 // ---- 60-byte blank padded strings (Fortran character(len=60)) ----
 inline void str60_set(char *t, const char *s) {
   size_t k = std::strlen(s);

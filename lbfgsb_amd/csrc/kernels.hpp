@@ -646,6 +646,19 @@ hipError_t launch_qn_draw(const Queue &q, int64_t n, WStore<T> w, int head, int 
                           const double *coef, double alpha, uint64_t seed, int64_t row0, int64_t s0, bool first,
                           const T *mean, QnOuts<T> out);
 
+// The stored pairs out of W and into it (k_qn_pairs.hip, lbfgsb_hip_qn_pairs_get / _set / _push).
+// The pairs c0 .. min(c0 + mc, col) - 1 (logical order, oldest first) -> s_out + c lds, y_out + c ldy, n rows each in
+// natural row order; lds, ldy >= n.  w.lmask may be set: the layout is read as it is.
+template <typename T>
+hipError_t launch_qn_pairs_get(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, T *s_out,
+                               int64_t lds, T *y_out, int64_t ldy);
+// The caller's columns s_in + j lds, y_in + j ldy, j < k <= m, -> the physical columns (slot0 + j) % m of W (natural
+// order: w.lmask must be NULL, the layout mask all ones), by 16-byte accesses where the caller's side is aligned for
+// them.
+template <typename T>
+hipError_t launch_qn_pairs_load(const Queue &q, int64_t n, WStore<T> w, int slot0, int k, const T *s_in, int64_t lds,
+                                const T *y_in, int64_t ldy);
+
 // ---- the active-set report (k_kkt.hip, solver_kkt.inl) ----
 // One pass over the caller's x, l, u, nbd, g: per row the status (iwhere codes), the signed projected gradient and the
 // bound multiplier into whichever of status / pg / mult is not NULL, and the KktSlots sums and maxima: partials into

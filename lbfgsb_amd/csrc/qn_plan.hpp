@@ -103,6 +103,24 @@ inline void qn_pack_coef(const QnPiece &p, int col, const double *cf, double *co
   }
 }
 
+// ---- the sums of a pushed pair (lbfgsb_hip_qn_pairs_push) ----
+// One W'V pass of the block (s, y) with its Gram carried: qn_plan(col, 2, QnCarry::Gram).  What qn_scatter_sums and
+// qn_scatter_carry make of it, by name: the 4 col sums against the stored pairs (logical order) and the three of the
+// pair itself.
+struct QnPushSums {
+  int col;
+  const double *w;  // qn_scatter_sums' out: 2 vectors x 2 col
+  const double *g;  // qn_scatter_carry's dst (Gram): entries a + b QN_KMAX, a <= b
+  double Ss(int j) const { return w[j]; }            // s_j's
+  double Ys(int j) const { return w[col + j]; }      // y_j's
+  double Sy(int j) const { return w[2 * col + j]; }  // s_j'y
+  double Yy(int j) const { return w[3 * col + j]; }  // y_j'y
+  double ss() const { return g[0]; }
+  double sy() const { return g[QN_KMAX]; }
+  double yy() const { return g[1 + QN_KMAX]; }
+  static constexpr int count(int col) { return 4 * col + 3; }
+};
+
 // ---- the basis pass (k_qn_eig.hip, lbfgsb_hip_qn_eigvec): OUT(n x k) = W(n x 2col) C(2col x k) ----
 // One launch per column tile writes ALL k <= QN_BASIS_KMAX outputs: the tiles are qn_plan's (from column 0, at most
 // QN_TILE pairs, capacity qn_mc), the first one stores its sums, every later one adds them to what is there (acc).

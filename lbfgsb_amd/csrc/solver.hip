@@ -1711,6 +1711,7 @@ class Solver final : public lbfgsb_hip_ctx {
                  void *g_, double factr, double pgtol, char *task, int iprint, char *csave,
                  int32_t *lsave, int32_t *isave_user, double *dsave) override {
     if (!task) return fail(LBFGSB_E_ARG, "setulb: NULL argument");
+    CHK(model_refuses(task));
     if (lbh::str60_eq(task, "START") || entry_mode == 0) {
       if (lbh::str60_eq(task, "START")) t = t_own, r = r_own;
       pp = false, entry_mode = 1, check_ptrs = true;
@@ -1732,6 +1733,7 @@ class Solver final : public lbfgsb_hip_ctx {
       return fail(LBFGSB_E_ARG, "setulb_dev_pp needs two distinct x and two distinct g buffers");
     for (const void *p : {(const void *)x1, (const void *)g1})
       if (((uintptr_t)p & 15) != 0) return fail(LBFGSB_E_ARG, "device pointers must be 16-byte aligned");
+    CHK(model_refuses(task));
     if (lbh::str60_eq(task, "START") || entry_mode == 0) {
       // (entry_mode == 0 without START: a run resumed from lbfgsb_hip_import_state -- the iterate and
       //  its gradient are in x0 / g0, the imported t and r in the context's own buffers)
@@ -1874,6 +1876,7 @@ class Solver final : public lbfgsb_hip_ctx {
 #include "solver_doors.inl"     // routine doors (active, errclb, cauchy, freev, formk, cmprlb, subsm, lnsrlb, matupd)
 #include "solver_qn.inl"        // the curvature model B, H = B^-1 as device operators (qn_apply, qn_diag)
 #include "solver_qn_idx.inl"    // its entries, sub-blocks and columns at index lists (qn_rows, qn_block, qn_cols)
+#include "solver_qn_pairs.inl"  // its stored pairs read back, loaded and appended to (qn_pairs_get / _set / _push)
 #include "solver_kkt.inl"       // the active set, the multipliers and the projected gradient (kkt, kkt_list)
 };
 

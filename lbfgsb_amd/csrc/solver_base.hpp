@@ -189,6 +189,11 @@ struct lbfgsb_hip_ctx {
   virtual int qn_shift_block(int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib, double *h_a,
                              int64_t lda) = 0;
   virtual int qn_shift_cols(int64_t k, const int64_t *h_idx, void *out, int64_t ldo) = 0;
+  // the stored pairs as device data (solver_qn_pairs.inl, lbfgsb_hip_qn_pairs_get / _set / _push)
+  virtual int qn_pairs_get(int32_t cap, int32_t *h_col, double *h_theta, void *s_out, int64_t lds, void *y_out,
+                           int64_t ldy) = 0;
+  virtual int qn_pairs_set(int32_t k, const void *s_in, int64_t lds, const void *y_in, int64_t ldy, double theta) = 0;
+  virtual int qn_pairs_push(const void *s, const void *y, double theta, int32_t *h_stored) = 0;
   // the active set, the multipliers and the projected gradient of the caller's arrays (solver_kkt.inl,
   // lbfgsb_hip_kkt / lbfgsb_hip_kkt_list)
   virtual int kkt(const void *x, const void *l, const void *u, const int32_t *nbd, const void *g, double tol,

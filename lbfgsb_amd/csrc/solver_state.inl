@@ -141,6 +141,7 @@
     qn.gen++;
     qn.have = true, qn.col = live_col, qn.head = live_head, qn.theta = 1.0, qn.theta_gram = true;
     qn.iupdat = isave_user[30], qn.nref = nrefresh;
+    model = 0;  // (the imported run replaces a caller's model)
     return 0;
   }
 

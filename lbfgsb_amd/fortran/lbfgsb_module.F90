@@ -55,6 +55,7 @@
       public :: lbfgsb_qn_shift_quad, lbfgsb_qn_shift_logpdf                              ! ... and densities
       public :: lbfgsb_qn_rows, lbfgsb_qn_block, lbfgsb_qn_cols       ! entries of B, H at lists of global 0-based rows
       public :: lbfgsb_qn_shift_block, lbfgsb_qn_shift_cols           ! ... and of (B + mu I + diag(d))^-1
+      public :: lbfgsb_qn_pairs_get, lbfgsb_qn_pairs_set, lbfgsb_qn_pairs_push  ! the stored pairs as device data
       integer,parameter,public :: LBFGSB_QN_IDX_MAXK = 4096
                                                        ! solves, log det and diagonal of (B + mu I + diag(d))^-1
       public :: lbfgsb_kkt, lbfgsb_kkt_list            ! the active set, the bound multipliers and the projected
@@ -340,6 +341,30 @@
             integer(c_int64_t) :: idx(*)
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_shift_cols
+         function lbfgsb_hip_qn_pairs_get(ctx,cap,col,theta,s,lds,y,ldy) bind(C,name='lbfgsb_hip_qn_pairs_get') result(rc)
+            import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, s, y
+            integer(c_int32_t),value :: cap
+            integer(c_int32_t) :: col
+            real(c_double) :: theta
+            integer(c_int64_t),value :: lds, ldy
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_pairs_get
+         function lbfgsb_hip_qn_pairs_set(ctx,k,s,lds,y,ldy,theta) bind(C,name='lbfgsb_hip_qn_pairs_set') result(rc)
+            import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, s, y
+            integer(c_int32_t),value :: k
+            integer(c_int64_t),value :: lds, ldy
+            real(c_double),value :: theta
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_pairs_set
+         function lbfgsb_hip_qn_pairs_push(ctx,s,y,theta,stored) bind(C,name='lbfgsb_hip_qn_pairs_push') result(rc)
+            import :: c_int, c_int32_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, s, y
+            real(c_double),value :: theta
+            integer(c_int32_t) :: stored
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_pairs_push
          function lbfgsb_hip_kkt(ctx,x,l,u,nbd,g,tol,pg,mult,status,cnt,val) bind(C,name='lbfgsb_hip_kkt') result(rc)
             import :: c_int, c_int64_t, c_double, c_ptr
             type(c_ptr),value :: ctx, x, l, u, nbd, g, pg, mult, status
@@ -860,6 +885,42 @@
       integer,intent(out) :: rc
       rc = lbfgsb_hip_qn_shift_cols(ctx, int(k, c_int64_t), idx, out, int(ldo, c_int64_t))
       end subroutine lbfgsb_qn_shift_cols
+
+      ! Pairs in and out (include/lbfgsb_hip.h, "Pairs in and out: a curvature model of the caller's own").  s, y are
+      ! DEVICE memory of the context's real kind: pair j (oldest first) at s + (j - 1) lds, y + (j - 1) ldy, n rows each.
+      ! lbfgsb_qn_pairs_get: col = the stored pairs, theta; cap = 0 (s, y = c_null_ptr) counts only.  lbfgsb_qn_pairs_set:
+      ! the context keeps the k <= m pairs as a model of the caller's own (it needs no run and ends the one it holds);
+      ! theta = 0: y'y / s'y of the newest pair.  lbfgsb_qn_pairs_push: one more pair into such a model as matupd stores
+      ! it; stored = 1, 0 (s'y not safely positive: nothing changed) or -1 (the model was reset to the empty one).
+      subroutine lbfgsb_qn_pairs_get(ctx, cap, col, theta, s, lds, y, ldy, rc)
+      type(c_ptr),intent(in) :: ctx, s, y
+      integer,intent(in) :: cap, lds, ldy
+      integer,intent(out) :: col, rc
+      real(c_double),intent(out) :: theta
+      integer(c_int32_t) :: c
+      c = 0_c_int32_t
+      theta = 0.0_c_double
+      rc = lbfgsb_hip_qn_pairs_get(ctx, int(cap, c_int32_t), c, theta, s, int(lds, c_int64_t), y, int(ldy, c_int64_t))
+      col = int(c)
+      end subroutine lbfgsb_qn_pairs_get
+
+      subroutine lbfgsb_qn_pairs_set(ctx, k, s, lds, y, ldy, theta, rc)
+      type(c_ptr),intent(in) :: ctx, s, y
+      integer,intent(in) :: k, lds, ldy
+      real(c_double),intent(in) :: theta
+      integer,intent(out) :: rc
+      rc = lbfgsb_hip_qn_pairs_set(ctx, int(k, c_int32_t), s, int(lds, c_int64_t), y, int(ldy, c_int64_t), theta)
+      end subroutine lbfgsb_qn_pairs_set
+
+      subroutine lbfgsb_qn_pairs_push(ctx, s, y, theta, stored, rc)
+      type(c_ptr),intent(in) :: ctx, s, y
+      real(c_double),intent(in) :: theta
+      integer,intent(out) :: stored, rc
+      integer(c_int32_t) :: st
+      st = 0_c_int32_t
+      rc = lbfgsb_hip_qn_pairs_push(ctx, s, y, theta, st)
+      stored = int(st)
+      end subroutine lbfgsb_qn_pairs_push
 
       ! The active set, the multipliers and the projected gradient (include/lbfgsb_hip.h, "The active set, the bound
       ! multipliers and the projected gradient as device data"): one pass over the device arrays x, l, u, nbd, g of

@@ -609,6 +609,79 @@ class DeviceSolver:
                                             lp.ctypes.data_as(C.POINTER(C.c_double))))
         return float(lp[0]) if x.dim() == 1 else lp
 
+    # ---- pairs in and out (include/lbfgsb_hip.h "Pairs in and out: a curvature model of the caller's own") ----
+    def _qn_pairs_arg(self, a, what, k=None):
+        """a (k, n) block of vectors (or (n,) for one) as a CUDA tensor of the context's kind, each vector contiguous;
+        a numpy array is copied to the device"""
+        import torch
+        if isinstance(a, np.ndarray):
+            a = torch.from_numpy(np.ascontiguousarray(a, self.real)).to(torch.device("cuda", self.device))
+        if a.dim() == 2 and a.shape[0] == 0:  # (no pair: nothing is read)
+            if a.shape[1] != self.n:
+                raise ValueError("%s must have shape (k, n) with n = %d" % (what, self.n))
+            return a
+        a = self._qn_vec(a, what)
+        if k is not None and (1 if a.dim() == 1 else a.shape[0]) != k:
+            raise ValueError("%s must hold %d vectors" % (what, k))
+        return a
+
+    def qn_pairs(self, out=None):
+        """(S, Y, theta): the stored pairs of the last return (or import_state, or of the caller's own model) as two
+        (col, n) tensors of this rank's rows, oldest pair first as qn_rows orders them, and theta -- read out of W in
+        the layout it is in, device to device; the run does not notice.  out: a pair (S, Y) of tensors of at least col
+        rows to write into (the first col rows are returned)."""
+        import torch
+        col, theta = C.c_int32(0), C.c_double(0.0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_pairs_get(self.h, 0, C.byref(col), C.byref(theta), None, 0, None, 0))
+        k = int(col.value)
+        dt = torch.float32 if self.real == np.float32 else torch.float64
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = (torch.empty((k, self.n), dtype=dt, device=dev), torch.empty((k, self.n), dtype=dt, device=dev))
+        S, Y = out
+        if k == 0:
+            return S[:0], Y[:0], theta.value
+        S, Y = self._qn_vec(S, "out[0]"), self._qn_vec(Y, "out[1]")
+        if S.dim() != 2 or Y.dim() != 2 or S.shape[0] < k or Y.shape[0] < k:
+            raise ValueError("out must be two tensors of shape (>= col, n), col = %d" % k)
+        check(self.lib.lbfgsb_hip_qn_pairs_get(self.h, k, C.byref(col), C.byref(theta), S.data_ptr(), S.stride(0),
+                                               Y.data_ptr(), Y.stride(0)))
+        self._qn_done()
+        return S[:k], Y[:k], theta.value
+
+    def qn_set_pairs(self, S, Y, theta=None):
+        """Make this context the keeper of a curvature model of the caller's own: S, Y of shape (k, n), k <= m, hold
+        the pairs (s_j, y_j) of this rank's rows, oldest first (CUDA tensors of the context's kind; numpy arrays are
+        copied to the device).  theta=None: y'y / s'y of the newest pair as the iteration sets it (1.0 with no pair).
+        Ends whatever run the context holds -- only a START follows -- and needs none: a DeviceSolver that has never
+        run takes pairs and then serves qn_apply, qn_operator(), qn_shift(...) and every other qn_* entry.  Raises
+        LbfgsbError (LBFGSB_E_ARG) for a pair with s'y <= 0 or a model that is not positive definite; the context
+        then holds no model.  Collective on sharded contexts."""
+        S, Y = self._qn_pairs_arg(S, "S"), self._qn_pairs_arg(Y, "Y")
+        k = 1 if S.dim() == 1 else int(S.shape[0])
+        if (1 if Y.dim() == 1 else int(Y.shape[0])) != k:
+            raise ValueError("S and Y must hold the same number of pairs")
+        if theta is None:
+            theta = 0.0 if k > 0 else 1.0
+        lds = self.n if S.dim() == 1 else S.stride(0)
+        ldy = self.n if Y.dim() == 1 else Y.stride(0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_pairs_set(self.h, k, S.data_ptr() if k else None, lds,
+                                               Y.data_ptr() if k else None, ldy, float(theta)))
+
+    def qn_push_pair(self, s, y, theta=None) -> int:
+        """Append one pair to the caller's model (after qn_set_pairs) as the iteration's update does: 1 when it was
+        stored (a full ring drops its oldest pair; theta = y'y / s'y unless given), 0 when s'y is not safely positive
+        and nothing changed, -1 when the update left the model indefinite and it was reset to the empty one.  One
+        pass over the pairs; the next qn_apply needs no Gram pass.  Collective on sharded contexts."""
+        s, y = self._qn_pairs_arg(s, "s", 1), self._qn_pairs_arg(y, "y", 1)
+        stored = C.c_int32(0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_pairs_push(self.h, s.data_ptr(), y.data_ptr(),
+                                                0.0 if theta is None else float(theta), C.byref(stored)))
+        return int(stored.value)
+
     def qn_operator(self, inverse: bool = True) -> "QnOperator":
         """H (default) or B as a small linear-operator object: hess_inv = sol.qn_operator() after minimize()."""
         return QnOperator(self, inverse)
