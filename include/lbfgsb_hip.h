@@ -882,7 +882,11 @@ int lbfgsb_hip_objective(lbfgsb_hip_ctx *ctx, int kind, const void *x, void *g, 
  *                           tile's run of layout-free entries of each stored column by 16-byte loads and hand them to
  *                           the lanes that own the rows through LDS (default 1) / two 8-byte loads per column in which
  *                           every lane takes part: the same values, the same sums, bit for bit
- *   "qn_basis" (0/1)        qn_eigvec writes all its vectors in one pass over W per tile of 16 pairs (default 1) / goes
+ *   "cw_ub" (0/1)           "cw_dense", all three bound arrays uniform (lbfgsb_hip_uniform_bounds: mask 7, no dictionary),
+ *                           m = 10 with the memory full: the lane-pair update pass reads l, u and nbd once per workgroup
+ *                           from the 64-byte buffers (default 1) / every row loads them, three loads of one address per
+ *                           trip: the same values, every result bit for bit (lbfgsb_hip_ub_launches counts the former)
+ *   "qn_basis" (0/1)       qn_eigvec writes all its vectors in one pass over W per tile of 16 pairs (default 1) / goes
  *                           through qn_apply's expansion, 4 vectors a pass: the same products summed in another order
  *   "uniform_bounds" (0/1)  detect bound arrays that hold one value each (lbfgsb_hip_uniform_bounds)
  *   "dict_bounds" (0/1)     dictionary-code bound arrays with <= 8 distinct values each (same place; default 1)

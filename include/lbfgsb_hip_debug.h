@@ -77,6 +77,10 @@ int lbfgsb_hip_compact_stats(lbfgsb_hip_ctx *ctx, int64_t *packs, int64_t *unpac
 /* Option "cw_dense": how often this context launched the storing pass's and the update pass's kernel with the dense
  * run loads (0 under cw_dense = 0, and for the shapes that have no such kernel: the update pass up to 5 pairs). */
 int lbfgsb_hip_dense_launches(lbfgsb_hip_ctx *ctx, int64_t *storing, int64_t *update);
+/* Option "cw_ub": how often of those the update pass's kernel was the form that reads l, u and nbd once per workgroup
+ * (0 under cw_ub = 0, with a uniform_bounds_mask other than 7, with dictionary-coded bounds and before the memory is
+ * full). */
+int lbfgsb_hip_ub_launches(lbfgsb_hip_ctx *ctx, int64_t *update);
 /* ONE host sync of the iteration timed by itself, `reps` times (microseconds: median and minimum): the
  * 8 min(m, 32) + 15 fp64 partials of the widest phase through the library's own fetch -- with a communicator the
  * all-gather over the ranks on the solver's stream (the sums of src/lbfgsb.f90:813-816, 2196-2244

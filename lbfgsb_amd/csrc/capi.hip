@@ -665,6 +665,12 @@ int lbfgsb_hip_dense_launches(lbfgsb_hip_ctx *ctx, int64_t *storing, int64_t *up
   return 0;
 }
 
+int lbfgsb_hip_ub_launches(lbfgsb_hip_ctx *ctx, int64_t *update) {
+  if (!ctx) return fail(LBFGSB_E_ARG, "ctx == NULL");
+  if (update) *update = ctx->ub_launches();
+  return 0;
+}
+
 int lbfgsb_hip_refresh_count(lbfgsb_hip_ctx *ctx, int64_t *count) {
   if (!ctx || !count) return fail(LBFGSB_E_ARG, "refresh_count: NULL argument");
   *count = ctx->nrefresh;

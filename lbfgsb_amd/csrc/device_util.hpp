@@ -334,6 +334,11 @@ __device__ __forceinline__ void raw_geti(const RawReg<W> &r, const int8_t *, int
 // register image of W elements of type E
 template <typename E, int W>
 using RawOf = RawReg<(int)sizeof(E) * W>;
+// ... that a trip declares only where it loads it (the uniform-bounds form of the layout's dense update pass has no
+// images of l, u, nbd: option "cw_ub")
+struct RawNone {};
+template <bool ON, typename R>
+using RawIf = std::conditional_t<ON, R, RawNone>;
 
 // ---- lane pairs (lane ^ 1): DPP quad_perm [1,0,3,2], no LDS traffic ----
 // (bound_ctrl = 1 with full row / bank masks: every lane is written and no source lane is out of range, so the

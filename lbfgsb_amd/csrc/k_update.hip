@@ -342,7 +342,9 @@ struct UpdScanPairTrip : NaturalRows<W> {
 // tile's first entry does today (see UpdScanTripCW1) -- such a row that does need its entries fetches them in
 // the kernel body as before (reload_cols).  A run of 64 entries that starts at an odd slot does not fit the 32
 // pieces: that trip loads as before (dense_).
-template <typename T, int MC, bool NT, bool TIGHT, bool DN = false>
+// UB (option "cw_ub"): l, u and nbd are one value each, which the kernel body holds since its prologue: the trip has
+// no register image of them and issues no load for them.
+template <typename T, int MC, bool NT, bool TIGHT, bool DN = false, bool UB = false>
 struct UpdScanPairTripCW : CwOneRow {
   static_assert(sizeof(T) == 8, "compact W: fp64");
   static constexpr int H = MC / 2;
@@ -350,9 +352,10 @@ struct UpdScanPairTripCW : CwOneRow {
   static constexpr bool DENSE = DN;
   bool dense_ = false;  // (wave-uniform) this trip's columns wait in the 16-byte images of the run
   int es_ = 0, re_ = 0;   // the run as loaded: in-tile slots [es_, re_)
-  RawOf<T, 1> rx, rl, ru, rg, rr, rd;
+  RawOf<T, 1> rx, rg, rr, rd;
+  RawIf<!UB, RawOf<T, 1>> rl, ru;
   RawOf<T, 2> ra[H], rb[H];
-  RawOf<nb_t, 1> rnb;
+  RawIf<!UB, RawOf<nb_t, 1>> rnb;
   RawOf<iw_t, 1> riw;
   typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
   typedef const __attribute__((address_space(1))) T *gptr;
@@ -378,12 +381,14 @@ struct UpdScanPairTripCW : CwOneRow {
     constexpr int B = (int)sizeof(T);
     this->ri_ = i, this->ws_ = slot, this->lf_ = lf;
     raw_issue<B, NT>(rx, c.x + i);
-    raw_issue<B, NT>(rl, (c.ub & 1) ? c.l : c.l + i);
-    raw_issue<B, NT>(ru, (c.ub & 2) ? c.u : c.u + i);
+    if constexpr (!UB) {
+      raw_issue<B, NT>(rl, (c.ub & 1) ? c.l : c.l + i);
+      raw_issue<B, NT>(ru, (c.ub & 2) ? c.u : c.u + i);
+    }
     raw_issue<B, NT>(rg, c.g + i);
     raw_issue<B, NT>(rr, c.r + i);
     raw_issue<B, NT>(rd, c.d + i);
-    raw_issue<1, false>(rnb, (c.ub & 4) ? c.nbd : c.nbd + i);
+    if constexpr (!UB) raw_issue<1, false>(rnb, (c.ub & 4) ? c.nbd : c.nbd + i);
     raw_issue<1, false>(riw, c.iwhere + i);
   }
   __device__ __forceinline__ bool dead_col(const UpdScanCtx<T> &c, int jj) const {  // (that table entry is the zero buffer)
@@ -493,7 +498,9 @@ struct UpdScanPairTripCW : CwOneRow {
 // plain instantiation on the few rows that remain.
 // CW: W in the tile-local free-row layout `lmask` (fp64, MC <= 10; for_tiles_cw)
 // DN: UpdScanPairTripCW's dense loads (CW && PAIR)
-template <typename T, int MC, bool NT, bool PIPE, bool NEWROW, bool PAIR, bool CW, bool TIGHT, bool DN>
+// UB: with DN, for uniform_bounds_mask = 7 without a dictionary (the caller checks): every l_i, u_i and nbd_i is the
+//     first entry of its 64-byte buffer, read once per workgroup here instead of once per row by every trip
+template <typename T, int MC, bool NT, bool PIPE, bool NEWROW, bool PAIR, bool CW, bool TIGHT, bool DN, bool UB = false>
 __device__ __forceinline__ void update_scan_body(
     int64_t n, const T *__restrict__ x, const T *__restrict__ l, const T *__restrict__ u,
     const nb_t *__restrict__ nbd, const T *__restrict__ g, const T *__restrict__ r,
@@ -530,6 +537,7 @@ __device__ __forceinline__ void update_scan_body(
     __syncthreads();
   }
   static_assert(!DN || (CW && PAIR), "dense loads: the layout's lane-pair instantiation");
+  static_assert(!UB || DN, "uniform bounds held by the body: the dense instantiation");
   __shared__ i32x4_t cw_scr[DN ? (BLOCK / 64) * 128 : 1];
   if constexpr (DN) {  // (every wave its own 2 KiB: no barrier)
     i32x4_t *own = cw_scr + (threadIdx.x >> 6) * 128 + (threadIdx.x & 63);
@@ -537,7 +545,11 @@ __device__ __forceinline__ void update_scan_body(
   }
   const UpdScanCtx<T> ctx{x, l, u, g, r, d, ws, wy, zero, nbd, iwhere, ldw, m, head, nold, ub, ptab, cw_scr};
   __shared__ T dict[16];
-  dict_fill<T>(dict, l, u, ub);
+  if constexpr (!UB) dict_fill<T>(dict, l, u, ub);
+  // UB: the values every row would load and convert (raw_issue / raw_get / raw_geti), from the same buffers
+  double ub_l = 0.0, ub_u = 0.0;
+  int ub_nb = 0;
+  if constexpr (UB) ub_l = (double)l[0], ub_u = (double)u[0], ub_nb = (int)nbd[0];
   using TripV = std::conditional_t<PAIR, UpdScanPairTrip<T, MC, V, NT>, UpdScanTrip<T, MC, V, NT>>;
   using Trip1 = std::conditional_t<PAIR, UpdScanPairTrip<T, MC, 1, NT>, UpdScanTrip<T, MC, 1, NT>>;
   auto body = [&](auto &tr, int64_t i, auto wt) {
@@ -545,14 +557,19 @@ __device__ __forceinline__ void update_scan_body(
     double xv[W], lv[W], uv[W], gv[W], rv[W], dv[W], tb[W], ng[W];
     int nb[W], iw[W];
     raw_get<W>(tr.rx, (const T *)nullptr, xv);
-    raw_get<W>(tr.rl, (const T *)nullptr, lv);
-    raw_get<W>(tr.ru, (const T *)nullptr, uv);
     raw_get<W>(tr.rg, (const T *)nullptr, gv);
     raw_get<W>(tr.rr, (const T *)nullptr, rv);
     raw_get<W>(tr.rd, (const T *)nullptr, dv);
-    raw_geti<W>(tr.rnb, (const nb_t *)nullptr, nb);
     raw_geti<W>(tr.riw, (const iw_t *)nullptr, iw);
-    dict_apply<T, W>(dict, ub, nb, lv, uv);
+    if constexpr (UB) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) lv[k] = ub_l, uv[k] = ub_u, nb[k] = ub_nb;
+    } else {
+      raw_get<W>(tr.rl, (const T *)nullptr, lv);
+      raw_get<W>(tr.ru, (const T *)nullptr, uv);
+      raw_geti<W>(tr.rnb, (const nb_t *)nullptr, nb);
+      dict_apply<T, W>(dict, ub, nb, lv, uv);
+    }
     bool iw_changed = false;
 #pragma unroll
     for (int k = 0; k < W; ++k) {
@@ -746,7 +763,7 @@ __device__ __forceinline__ void update_scan_body(
     if constexpr (!PAIR) row_stores();
   };
   if constexpr (CW && PAIR)  // (the caller passes whole tiles)
-    for_halves_cw<UpdScanPairTripCW<T, MC, NT, TIGHT, DN>>(n, ctx, lmask, body);
+    for_halves_cw<UpdScanPairTripCW<T, MC, NT, TIGHT, DN, UB>>(n, ctx, lmask, body);
   else if constexpr (CW && NEWROW)  // (one row per lane and trip, two trips in flight: see for_halves_cw)
     for_halves_cw<UpdScanTripCW1<T, MC, NT>>(n, ctx, lmask, body);
   else if constexpr (CW)
@@ -796,6 +813,20 @@ __global__ __launch_bounds__(BLOCK) void update_scan_kernel_dense(
     int store_iw, double cand_hi, uint64_t *ckeys, uint32_t *cidx, uint32_t ccap, uint32_t *ccount,
     int ub, double *part, const uint64_t *__restrict__ lmask) {
   update_scan_body<T, MC, NT, false, true, true, true, TIGHT, true>(
+      n, x, l, u, nbd, g, r, d, dimpl, stp, iwhere, tbrk, ws, wy, zero, ldw, m, head, nold, itail, store_pair, store_iw,
+      cand_hi, ckeys, cidx, ccap, ccount, ub, part, lmask);
+}
+// ... and with uniform bounds held by the body (option "cw_ub"; launched only with uniform_bounds_mask = 7, no
+// dictionary)
+template <typename T, int MC, bool NT, bool TIGHT>
+__global__ __launch_bounds__(BLOCK) void update_scan_kernel_dense_ub(
+    int64_t n, const T *__restrict__ x, const T *__restrict__ l, const T *__restrict__ u,
+    const nb_t *__restrict__ nbd, const T *__restrict__ g, const T *__restrict__ r,
+    const T *__restrict__ d, int dimpl, double stp, iw_t *iwhere, T *tbrk, T *ws, T *wy,
+    const T *__restrict__ zero, int64_t ldw, int m, int head, int nold, int itail, int store_pair,
+    int store_iw, double cand_hi, uint64_t *ckeys, uint32_t *cidx, uint32_t ccap, uint32_t *ccount,
+    int ub, double *part, const uint64_t *__restrict__ lmask) {
+  update_scan_body<T, MC, NT, false, true, true, true, TIGHT, true, true>(
       n, x, l, u, nbd, g, r, d, dimpl, stp, iwhere, tbrk, ws, wy, zero, ldw, m, head, nold, itail, store_pair, store_iw,
       cand_hi, ckeys, cidx, ccap, ccount, ub, part, lmask);
 }
@@ -905,7 +936,12 @@ void launch_update_scan(Queue &q, int64_t n, const T *x, const T *l, const T *u,
 #define LB_PAIR_CW(NTV, TIGHTV)                                                      \
   { if (q.cw_dense) { q.n_dense_update++; LB_PAIR_CW_(update_scan_kernel_dense<T, 10, NTV, TIGHTV>) } \
     else LB_PAIR_CW_(update_scan_kernel<T, 10, NTV, false, true, true, true, TIGHTV>) }
-          if (nold == 9) {
+          // (the steady state under uniform bounds: the form that holds them, option "cw_ub")
+          if (nold == 9 && q.cw_dense && q.cw_ub && (ub & 7) == 7 && !(ub & UB_DICT)) {
+            q.n_dense_update++, q.n_ub_update++;
+            if (q.nt) LB_PAIR_CW_(update_scan_kernel_dense_ub<T, 10, true, true>)
+            else LB_PAIR_CW_(update_scan_kernel_dense_ub<T, 10, false, true>)
+          } else if (nold == 9) {
             if (q.nt) LB_PAIR_CW(true, true) else LB_PAIR_CW(false, true)
           } else {
             if (q.nt) LB_PAIR_CW(true, false) else LB_PAIR_CW(false, false)

@@ -68,6 +68,10 @@ struct Queue {
   bool nt = false;  // nontemporal loads in the W-pass kernels (W much larger than the Infinity Cache)
   bool cw_dense = true;  // option "cw_dense": the layout's passes fetch a tile's run of a column by 16-byte loads
   int64_t n_dense_subsm = 0, n_dense_update = 0;  // launches of the two dense kernels (lbfgsb_hip_dense_launches)
+  // option "cw_ub": under uniform_bounds_mask = 7 the steady-state dense update kernel reads l, u, nbd once per
+  // workgroup
+  bool cw_ub = true;
+  int64_t n_ub_update = 0;  // launches of that form, counted in n_dense_update too (lbfgsb_hip_ub_launches)
   Tune tune{};
   // first kernel launch that failed since the last check (hipGetLastError right behind the launch,
   // so that the error is reported with the kernel's name and not at the next stream sync)

@@ -281,6 +281,7 @@ struct lbfgsb_hip_ctx {
   hipEvent_t return_ev = nullptr;                                                // lbfgsb_hip_return_event
   virtual void compact_stats(int64_t &packs, int64_t &unpacks, int &packed, int &eligible) const = 0;
   virtual void dense_launches(int64_t &storing, int64_t &update) const = 0;
+  virtual int64_t ub_launches() const = 0;
   virtual int64_t skip_scans_reused() const = 0;
   virtual void defer_counts(int64_t &deferred, int64_t &reissued) const = 0;
   // a built-in objective whose value is still on the device (d_res[0], to be scaled by f_scale):

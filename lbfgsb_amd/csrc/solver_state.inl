@@ -307,6 +307,7 @@
   void dense_launches(int64_t &storing, int64_t &update) const override {
     storing = q.n_dense_subsm, update = q.n_dense_update;
   }
+  int64_t ub_launches() const override { return q.n_ub_update; }
   void compact_stats(int64_t &packs, int64_t &unpacks, int &packed, int &eligible) const override {
     packs = ncw_pack, unpacks = ncw_unpack, packed = cw_packed ? 1 : 0, eligible = cw_eligible() ? 1 : 0;
   }

@@ -460,6 +460,7 @@
     }
     if (k == "compact_policy") return in_range(0, 2, cw_policy);
     if (k == "cw_dense") return flag(q.cw_dense);  // 0: the layout's passes load W as before (8 bytes per lane and row)
+    if (k == "cw_ub") return flag(q.cw_ub);  // 0: the dense update pass loads l, u, nbd per row under uniform bounds too
     if (k == "two_pass") return flag(two_pass);
     if (k == "two_pass_maxcol") return in_range(0, lbk::MAXM, two_pass_maxcol);
     if (k == "lean") return flag(lean_on);

@@ -921,6 +921,12 @@ class DeviceSolver:
         check(self.lib.lbfgsb_hip_dense_launches(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def ub_launches(self):
+        """option cw_ub: launches of the update pass's uniform-bounds form -- lbfgsb_hip_ub_launches"""
+        a = C.c_int64(0)
+        check(self.lib.lbfgsb_hip_ub_launches(self.h, C.byref(a)))
+        return a.value
+
     def compact_stats(self):
         """option compact_w: (packs, unpacks, packed now, eligible) -- lbfgsb_hip_compact_stats"""
         a, b = C.c_int64(0), C.c_int64(0)
