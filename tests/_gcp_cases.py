@@ -361,7 +361,7 @@ def case(name):
 
 def oracle_cauchy(c, perm=None):
     """the oracle's double-precision cauchy (oracle/lbfgsb_oracle.c, the twin of src/lbfgsb.f90:1157-1532) on the
-    case's numbers -> dict(nseg, info, iwhere, xcp, c, tsum, sbgnrm).  REAL32 cases: their float32 numbers widened,
+    case's numbers -> dict(nseg, info, iwhere, xcp, c, tsum, sbgnrm, p, wbp, v).  REAL32 cases: their float32 numbers widened,
     epsmch of float32 -- the times of their breakpoints are exact quotients and do not change.  perm: the same
     problem with its rows in another order (iwhere and xcp come back in the case's order).  tsum is read off the
     probe row where the case has one (exact), else off a moving row ((xcp - x) / d: two more roundings)."""
@@ -389,7 +389,8 @@ def oracle_cauchy(c, perm=None):
         i = int(np.flatnonzero(d != 0)[0])
         tsum = float((xcp[i] - x[i]) / d[i])
     return dict(nseg=int(nseg[0]), info=int(info[0]), iwhere=iw[back], xcp=xcp[back], c=pc[1][:2 * c.col].copy(),
-                tsum=tsum, sbgnrm=sbg)
+                tsum=tsum, sbgnrm=sbg, p=pc[0][:2 * c.col].copy(), wbp=pc[2][:2 * c.col].copy(),
+                v=pc[3][:2 * c.col].copy())
 
 
 EPS64 = EPS[np.float64]

@@ -25,6 +25,10 @@ The work vectors p, wbp and v are NOT compared: the search leaves p = W'd of the
 where the reference's walk leaves the last breakpoint's.  Nothing reads them after cauchy(): wbp and v are local to
 it, p (wa(1:2m)) is overwritten by cmprlb's M c before anything reads it, and closed_ok -- which would hand p to
 the subspace step -- stays false on this path.
+
+The DEFAULT walk -- a context without the flag, what every iteration runs -- goes through the same cases and the same
+assertions in test_default_walk_against_the_extended_precision_walk, minus those about the search itself, plus p, wbp
+and v against the oracle's: the sequential walk does leave them.
 """
 import numpy as np
 import pytest
@@ -66,19 +70,24 @@ def _door(c, sbgnrm, flag=True):
         sol.close()
     w8 = wa2[off["wa8m"][0]:off["wa8m"][0] + 8 * m]
     return dict(nseg=nseg, info=info, sorts=sorts, iwhere=iwa2[n:2 * n].copy(), xcp=xcp_d.cpu().numpy(),
-                z=wa2[off["z"][0]:off["z"][0] + n].copy(), c=w8[2 * m:2 * m + 2 * c.col].astype(np.float64))
+                z=wa2[off["z"][0]:off["z"][0] + n].copy(), c=w8[2 * m:2 * m + 2 * c.col].astype(np.float64),
+                p=w8[:2 * c.col].astype(np.float64), wbp=w8[4 * m:4 * m + 2 * c.col].astype(np.float64),
+                v=w8[6 * m:6 * m + 2 * c.col].astype(np.float64))
 
 
-@pytest.mark.parametrize("name", gc.NAMES)
-def test_one_call_against_the_extended_precision_walk(oracle_built, name):
+def _compare(name, got, search):
+    """what one r_cauchy call left (got, of _door) against the extended-precision walk of the case; search: the call
+    went through a context with the flag, and the assertions about the search itself apply"""
     c, tr = gc.case(name)
     ref = gc.reference(name)
-    got = _door(c, ref["sbgnrm"])
     eps_T = gc.EPS[c.real]
     r32 = c.real == np.float32
 
     # ---- the path ran
-    assert got["sorts"] == (1 if c.path == "search" else 0), "full sorts of the parallel search: %d" % got["sorts"]
+    if search:
+        assert got["sorts"] == (1 if c.path == "search" else 0), "full sorts of the parallel search: %d" % got["sorts"]
+    else:
+        assert got["sorts"] == 0, "a context without the flag sorted: %d" % got["sorts"]
 
     # ---- integers and sets
     assert (got["nseg"], got["info"]) == (tr.nseg, 0), (got["nseg"], tr.nseg)
@@ -96,7 +105,7 @@ def test_one_call_against_the_extended_precision_walk(oracle_built, name):
             rho_t = gc.rho_t(t_gpu, tr)
             assert abs(np.longdouble(t_gpu) - tr.tsum) <= E_t + (eps_T * tsum if r32 else 0.0), \
                 "tsum (%s): rho_gpu %.3g, bound K_t %.3g (rho_ref %.3g)" % (key, rho_t, ref["K_t"], ref["rho_t"])
-        if c.path == "closed":
+        if search and c.path == "closed":
             assert -got["z"][i] / scale == 1.0 / c.theta, "the closed form's tsum is fl(1 / theta)"
 
     # ---- c
@@ -129,8 +138,48 @@ def test_one_call_against_the_extended_precision_walk(oracle_built, name):
         assert np.all(err <= tol), "%s: moving row %d off by %.3e > %.3e" % (key, np.flatnonzero(moving)[k], err[k], tol[k])
 
     # ---- the guard's fallback is the exact walk: bit for bit what a context without the flag returns
-    if c.path == "fallback":
+    if search and c.path == "fallback":
         plain = _door(c, ref["sbgnrm"], flag=False)
         assert (plain["nseg"], plain["info"], plain["sorts"]) == (got["nseg"], 0, 0)
         assert np.array_equal(plain["iwhere"], got["iwhere"])
         assert np.array_equal(plain["z"], got["z"]) and np.array_equal(plain["xcp"], got["xcp"])
+
+
+@pytest.mark.parametrize("name", gc.NAMES)
+def test_one_call_against_the_extended_precision_walk(oracle_built, name):
+    c, _ = gc.case(name)
+    _compare(name, _door(c, gc.reference(name)["sbgnrm"]), search=True)
+
+
+@pytest.mark.parametrize("name", gc.NAMES)
+def test_default_walk_against_the_extended_precision_walk(oracle_built, name):
+    """The walk EVERY iteration runs (a context without the flag: the provider and the host replay of cauchy() in
+    solver_walk.inl), one call deep on the same cases and held to the same truth with the same bounds: nseg, info, the
+    whole iwhere, c, tsum at the probe row, xcp.  What is about the search itself is left out (the sort counter stays
+    0 here, and a walk reaches fl(1 / theta) only up to its rounding).  The sequential walk does leave p, wbp and v
+    the way the reference's does -- p = W'd over the rows that still move, wbp and v = M wbp of the last breakpoint
+    it crossed (untouched where it crossed none) -- so these are compared with the oracle's, 1e-9 of their largest
+    entry; a REAL32 context exports them as float32, one rounding of each entry, which the bound allows for as the
+    bound on c does.  p's largest entry is taken over the call: the walk starts from W'd over all moving rows and takes
+    the crossed rows' terms away again, so that what is left can be a remainder of cancellation alone -- all_crossed_bnded
+    ends with p = 0 in exact arithmetic (the oracle leaves 2e-14, the library 0 or as little), clamp with 1e-9 of its
+    starting value, known to 2e-15 in either code: errors of the size of an ulp of the START value, which is therefore
+    part of the scale."""
+    c, tr = gc.case(name)
+    got = _door(c, gc.reference(name)["sbgnrm"], flag=False)
+    _compare(name, got, search=False)
+    if not c.col:
+        return
+    o = gc.oracle_cauchy(c)
+    assert (o["nseg"], o["info"]) == (got["nseg"], 0)
+    crossed = tr.ks - (1 if tr.all_fixed else 0)       # (the all-fixed exit :1436 leaves before wbp is written)
+    eps_x = gc.EPS[c.real] if c.real == np.float32 else 0.0
+    ring = [(c.head - 1 + j) % c.m for j in range(c.col)]
+    d0 = np.where((tr.d != 0) | tr.fixed, -c.g, 0).astype(np.float64)      # the direction the walk starts with
+    p0 = np.concatenate([c.wy[ring].astype(np.float64) @ d0, c.theta * (c.ws[ring].astype(np.float64) @ d0)])
+    for key in ("p",) + (("wbp", "v") if crossed > 0 else ()):
+        a, b = got[key], o[key]
+        top = max(float(np.max(np.abs(b))), float(np.max(np.abs(p0))) if key == "p" else 0.0)
+        tol = 1e-9 * top + eps_x * np.abs(b)
+        k = int(np.argmax(np.abs(a - b) - tol))
+        assert np.all(np.abs(a - b) <= tol), "%s[%d]: %r vs the oracle's %r" % (key, k, a[k], b[k])

@@ -1,7 +1,9 @@
 """REAL32 context (BASELINE.json configs[4], reference -DREAL32, lbfgsb_kinds_module.F90:29-37):
 fp32 storage and kernels, fp64 partial sums and host algebra.  The reference's REAL32 build
 does everything in fp32, so agreement is a tolerance sweep, not bit parity:
-f must agree with the REAL64 oracle to ~1e-6 and with the REAL32 oracle to fp32 noise."""
+f must agree with the REAL64 oracle to ~1e-6 and with the REAL32 oracle to fp32 noise.
+One routine deep, with derived bars (bit for bit / 1e-12 of the fp64 sums / 4 x the REAL32 oracle's own error) and at
+n = 1 ... 150001 with every fp32 tail: tests/test_gpu_routines_real32.py (helper tests/_r32_truth.py)."""
 import numpy as np
 import pytest
 
