@@ -570,6 +570,49 @@ int lbfgsb_hip_import_state(lbfgsb_hip_ctx *ctx, const void *wa, const int32_t *
  * that is too small, an index outside 0 .. n_global - 1, a mode that is not B or H.  When, REAL32 (W and out fp32,
  * every sum and host result fp64) and the refusals are qn_apply's, and the run does not notice the calls.
  *
+ * The model over a range of shifts.  A trust-region or Levenberg-Marquardt step looks for the mu with
+ * ||(B + mu I)^-1 g|| = Delta, evidence maximisation over a prior precision tau needs log det (B + tau I) at dozens of
+ * tau: questions about many shifts, each of which would cost a qn_shift_set.  When the diagonal is "pins plus a scalar"
+ * they cost the device nothing: with F the rows that are not pinned, R = [S, Y] and w = 1 / (theta + mu), the weighted
+ * Gram of qn_shift_set is w G_F, G_F = R_F'R_F, and p = R_F'v does not depend on mu.  From one Gram and one read pass
+ * per vector the host has, for x(mu) = (B_FF + mu I)^-1 v_F = w 1_F o (v + R c(mu)) and vv = sum_F v_i^2,
+ *   ||x||^2 = w^2 (vv + 2 c'p + c'G_F c),   v'x = w (vv + p'c),   d||x||^2 / d mu = -2 x'(B_FF + mu I)^-1 x,
+ *   log det (B_FF + mu I) = nf log(theta + mu) + log |det K(mu)| - log |det M^-1|,   K(mu) = M^-1 - w G_F in W's basis,
+ * at any number of shifts.
+ *   qn_path_set: status (device int8 codes as lbfgsb_hip_kkt writes them, or NULL: nothing pinned) and code_mask (bit
+ *     (code + 1) selects a code to PIN, lbfgsb_hip_kkt_list's convention: 0b11100 pins the rows at a lower bound, at
+ *     an upper bound or fixed) give one free / pinned byte per row in a buffer of the context; *h_pinned (may be NULL)
+ *     receives the pinned rows over all ranks.  G_F is reduced by ceil(2col / 4) masked passes over W; with no pinned
+ *     row it is the pairs' cached Gram and no pass is launched.  All rows pinned is legal.  At most
+ *     LBFGSB_QN_ROOT_MAXCOL stored pairs (LBFGSB_E_ARG).  Independent of qn_shift_set: both may be live.
+ *   qn_path_logdet: host only, any k >= 1, nothing launched.  h_info[j] = 0: h_logdet[j] = log det (B_FF + h_mu[j] I);
+ *     1: theta + mu_j <= 0 or mu_j not finite; 2: K does not have the inertia (col, col) -- the shifted model is not
+ *     positive definite on the free rows.  h_logdet[j] is written only where h_info[j] = 0; the call returns 0 all the
+ *     same.
+ *   qn_path_solve: out + j*ldo receives x(h_mu[j]), j < k <= LBFGSB_QN_PATH_MAXK, in the context's real kind and
+ *     natural row order; a pinned row is +0 whatever v holds there.  h_norm2[j] = ||x_j||^2 and h_vx[j] = v'x_j by the
+ *     formulas above; either may be NULL, and out may be NULL when one of them is given (the read pass alone).  out
+ *     may not overlap v (the caller's responsibility, as in qn_shift_solve: not checked).  A bad mu_j is
+ *     LBFGSB_E_ARG (info 1) or LBFGSB_E_STATE (info 2), the message names j, nothing is written.  One read pass over W, then one pass per tile of 16 pairs that stores all k outputs (2col*8 + 8 + 1
+ *     + 8k B per row and tile in fp64).
+ *   qn_path_trust: step = -(B_FF + mu I)^-1 g_F with mu >= 0, ||step|| <= delta and mu (delta - ||step||) = 0 to
+ *     rtol: mu = 0 when ||x(0)|| <= delta (the Newton step of the free variables), else Newton on 1 / ||x(mu)|| -
+ *     1 / delta from mu = 0 inside a bracket that bisects whenever Newton leaves it, until | ||x|| - delta | <= rtol
+ *     delta or the ends of the bracket are adjacent doubles; max_it bounds the evaluations.  rtol = 0 and max_it = 0
+ *     select 1e-10 and 100.  h_res = {mu, ||step||, the predicted decrease g'x / 2 + mu ||x||^2 / 2, on_boundary (0 /
+ *     1)}, *h_iters the host evaluations made.  on_boundary = 1 says mu > 0, the constraint is active; ||step|| =
+ *     delta then holds to rtol unless the iteration ended by max_it or by adjacent doubles, when the step is the one
+ *     at the upper end of the bracket: ||step|| <= delta (1 + rtol) always, and h_res[1] says what it is.  If max_it
+ *     evaluations find no shift with ||step|| <= delta at all (max_it = 1 outside the region, say) the call returns
+ *     LBFGSB_E_STATE and writes nothing: never a step outside the region (to rtol).  step may be NULL (the scalars
+ *     alone).  With g_F = 0 or every row pinned step is +0 and h_res = {0, 0, 0, 0}.  The read pass, plus one write pass per tile when step is given; the
+ *     secular iterations launch nothing.  LBFGSB_E_ARG: delta not > 0 or not finite, rtol outside [0, 1), max_it < 0,
+ *     g NULL.
+ * The result of qn_path_set belongs to the pairs it was made of: after a return that changes the pairs or theta the
+ * other three return LBFGSB_E_STATE ("call qn_path_set again").  Host results have the same bits on every rank.  When,
+ * streams, LBFGSB_F_NO_RETURN_SYNC, the collective rule, REAL32 (v, out fp32; the bytes, every sum and every host
+ * number fp64) and the refusals are qn_shift_solve's, and the run does not notice the calls.
+ *
  * Pairs in and out: a curvature model of the caller's own.  The stored pairs (s_j, y_j) and theta are all that the
  * entries above read; these three move them as DEVICE data, with no run required and nothing of the reference's wa
  * through host memory.  S, Y, s, y are device memory of the context's real kind: pair j (oldest first, as qn_rows
@@ -645,6 +688,13 @@ int lbfgsb_hip_qn_cols(lbfgsb_hip_ctx *ctx, int mode, int64_t k, const int64_t *
 int lbfgsb_hip_qn_shift_block(lbfgsb_hip_ctx *ctx, int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib,
                               double *h_a, int64_t lda);
 int lbfgsb_hip_qn_shift_cols(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_idx, void *out, int64_t ldo);
+#define LBFGSB_QN_PATH_MAXK 64
+int lbfgsb_hip_qn_path_set(lbfgsb_hip_ctx *ctx, const int8_t *status, int code_mask, int64_t *h_pinned);
+int lbfgsb_hip_qn_path_logdet(lbfgsb_hip_ctx *ctx, int64_t k, const double *h_mu, double *h_logdet, int32_t *h_info);
+int lbfgsb_hip_qn_path_solve(lbfgsb_hip_ctx *ctx, const void *v, int64_t k, const double *h_mu, void *out,
+                             int64_t ldo, double *h_norm2, double *h_vx);
+int lbfgsb_hip_qn_path_trust(lbfgsb_hip_ctx *ctx, const void *g, double delta, double rtol, int max_it, void *step,
+                             double *h_res /*[4]*/, int32_t *h_iters);
 int lbfgsb_hip_qn_pairs_get(lbfgsb_hip_ctx *ctx, int32_t cap, int32_t *h_col, double *h_theta, void *S, int64_t lds,
                             void *Y, int64_t ldy);
 int lbfgsb_hip_qn_pairs_set(lbfgsb_hip_ctx *ctx, int32_t k, const void *S, int64_t lds, const void *Y, int64_t ldy,

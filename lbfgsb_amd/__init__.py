@@ -8,6 +8,7 @@ a gfx950 device is missing.
 """
 from .capi import LbfgsbError, lib_path, load_library, build_library  # noqa: F401
 from .solver import DeviceSolver, QnOperator, QnShifted, KktReport, setulb, wa_length, TASK_LEN  # noqa: F401
+from .solver import QnPath, TrustStep  # noqa: F401
 from .capi import QN_B, QN_H, QN_B_SQRT, QN_H_SQRT  # noqa: F401
 from .distributed import block_partition, attach_rccl, attach_host_group  # noqa: F401
 

@@ -89,6 +89,13 @@ PROTOTYPES = {
     "lbfgsb_hip_qn_shift_quad": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(C.c_double)]),
     "lbfgsb_hip_qn_shift_logpdf": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_double,
                                              C.POINTER(C.c_double)]),
+    "lbfgsb_hip_qn_path_set": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int64)]),
+    "lbfgsb_hip_qn_path_logdet": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int32)]),
+    "lbfgsb_hip_qn_path_solve": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_double), _vp, C.c_int64,
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lbfgsb_hip_qn_path_trust": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_int, _vp, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_int32)]),
     "lbfgsb_hip_kkt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "lbfgsb_hip_kkt_list": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int64, _vp]),
     "lbfgsb_hip_import_state": (C.c_int, [_vp, _vp, _vp, _vp]),
@@ -132,6 +139,7 @@ E_NOGPU, E_ARG, E_ALLOC, E_COMM, E_STATE = -100, -101, -102, -103, -104   # stat
 QN_B, QN_H = 0, 1  # lbfgsb_hip_qn_apply / lbfgsb_hip_qn_diag: the model B, its inverse H = B^-1
 QN_B_SQRT, QN_H_SQRT = 4, 5  # lbfgsb_hip_qn_apply only: the symmetric square roots B^(1/2), H^(1/2)
 QN_ROOT_MAXCOL = 64
+QN_PATH_MAXK = 64  # lbfgsb_hip_qn_path_solve: the most shifts of a call
 QN_IDX_MAXK = 4096  # lbfgsb_hip_qn_rows / qn_block / qn_shift_block: the longest index list of a call
 QN_EIG_CUT = 1e-8  # lbfgsb_hip_qn_eig: directions with |lambda - bulk| <= QN_EIG_CUT * bulk count as bulk
 # lbfgsb_hip_kkt: the slots of h_cnt and h_val (LBFGSB_KKT_* without the prefix, in index order) -- the field names

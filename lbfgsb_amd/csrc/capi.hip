@@ -392,6 +392,35 @@ int lbfgsb_hip_qn_shift_cols(lbfgsb_hip_ctx *ctx, int64_t k, const int64_t *h_id
   if (k < 1 || k > 128 || ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_shift_cols: k < 1, k > 128 or ldo < n_local");
   return ctx->qn_shift_cols(k, h_idx, out, ldo);
 }
+// the model along a path of shifts
+static_assert(LBFGSB_QN_PATH_MAXK == lbk::QN_PATH_MAXK, "the header's cap is the expansion's");
+int lbfgsb_hip_qn_path_set(lbfgsb_hip_ctx *ctx, const int8_t *status, int code_mask, int64_t *h_pinned) {
+  if (!ctx) return fail(LBFGSB_E_ARG, "qn_path_set: NULL argument");
+  if (code_mask < 0 || code_mask > 31) return fail(LBFGSB_E_ARG, "qn_path_set: code_mask outside 0 .. 31");
+  return ctx->qn_path_set(status, code_mask, h_pinned);
+}
+int lbfgsb_hip_qn_path_logdet(lbfgsb_hip_ctx *ctx, int64_t k, const double *h_mu, double *h_logdet, int32_t *h_info) {
+  if (!ctx || !h_mu || !h_logdet || !h_info) return fail(LBFGSB_E_ARG, "qn_path_logdet: NULL argument");
+  if (k < 1) return fail(LBFGSB_E_ARG, "qn_path_logdet: k < 1");
+  return ctx->qn_path_logdet(k, h_mu, h_logdet, h_info);
+}
+int lbfgsb_hip_qn_path_solve(lbfgsb_hip_ctx *ctx, const void *v, int64_t k, const double *h_mu, void *out,
+                             int64_t ldo, double *h_norm2, double *h_vx) {
+  if (!ctx || !v || !h_mu) return fail(LBFGSB_E_ARG, "qn_path_solve: NULL argument");
+  if (!out && !h_norm2 && !h_vx) return fail(LBFGSB_E_ARG, "qn_path_solve: neither out nor h_norm2 nor h_vx");
+  if (k < 1 || k > LBFGSB_QN_PATH_MAXK) return fail(LBFGSB_E_ARG, "qn_path_solve: k < 1 or k > LBFGSB_QN_PATH_MAXK");
+  if (out && ldo < ctx->n) return fail(LBFGSB_E_ARG, "qn_path_solve: ldo < n_local");
+  return ctx->qn_path_solve(v, k, h_mu, out, ldo, h_norm2, h_vx);
+}
+int lbfgsb_hip_qn_path_trust(lbfgsb_hip_ctx *ctx, const void *g, double delta, double rtol, int max_it, void *step,
+                             double *h_res, int32_t *h_iters) {
+  if (!ctx || !g || !h_res || !h_iters) return fail(LBFGSB_E_ARG, "qn_path_trust: NULL argument");
+  if (!(delta > 0.0) || !std::isfinite(delta))
+    return fail(LBFGSB_E_ARG, "qn_path_trust: delta is not > 0 or not finite");
+  if (!(rtol >= 0.0 && rtol < 1.0)) return fail(LBFGSB_E_ARG, "qn_path_trust: rtol outside [0, 1)");
+  if (max_it < 0) return fail(LBFGSB_E_ARG, "qn_path_trust: max_it < 0");
+  return ctx->qn_path_trust(g, delta, rtol, max_it, step, h_res, h_iters);
+}
 int lbfgsb_hip_qn_pairs_get(lbfgsb_hip_ctx *ctx, int32_t cap, int32_t *h_col, double *h_theta, void *S, int64_t lds,
                             void *Y, int64_t ldy) {
   if (!ctx || !h_col || !h_theta) return fail(LBFGSB_E_ARG, "qn_pairs_get: NULL argument");

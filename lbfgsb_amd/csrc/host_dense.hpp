@@ -315,6 +315,124 @@ inline int qn_shift_coef(int col, double theta, const double *kf, const double *
   return 0;
 }
 
+// ---- the model along a path of shifts (lbfgsb_hip_qn_path_*, solver_qn_path.inl) ----
+// When the diagonal is "pins plus a scalar", every free row has the same weight w = 1 / (theta + mu), the weighted Gram
+// of qn_shift_factor is w G_F with G_F = R_F'R_F, R = [S, Y] on the free rows F, and p = R_F'v does not depend on mu
+// either: from one Gram and one read pass per vector the host answers for any number of shifts.
+//
+// kf, *logdet = qn_shift_factor's for the weighted Gram w g_f (g_f: 2col x 2col, the S block first; sy, sts: col x col
+// as qn_shift_factor reads them, leading dimension col).  work: 4 col^2 doubles.  Returns qn_shift_factor's info.
+inline int qn_path_factor(int col, double theta, const double *sy, const double *sts, const double *g_f, double w,
+                          double *kf, double *logdet, double *work) {
+  const int d = 2 * col;
+  for (size_t e = 0; e < (size_t)d * d; ++e) work[e] = w * g_f[e];
+  return qn_shift_factor(col, theta, sy, col, sts, col, work, kf, logdet);
+}
+
+// The shift mu judged and factorised: returns 1 when theta + mu <= 0 or mu is not finite, 2 when K(mu) does not have
+// the inertia (col, col) -- the shifted model is not positive definite on the free rows --, else 0 with *w =
+// 1 / (theta + mu), kf and *logdet = log det (B_FF + mu I) = nf log(theta + mu) + log |det K| - ldm (ldm = log |det
+// M^-1|, qn_shift_factor without a Gram; nf = 0, no free row: 0).  work: 4 col^2 doubles.
+inline int qn_path_shift(int col, double theta, double mu, const double *sy, const double *sts, const double *g_f,
+                         double nf, double ldm, double *kf, double *w, double *logdet, double *work) {
+  const double shift = theta + mu;
+  if (!std::isfinite(mu) || !(shift > 0.0)) return 1;
+  *w = 1.0 / shift;
+  double ldk = 0.0;
+  if (col > 0 && qn_path_factor(col, theta, sy, sts, g_f, *w, kf, &ldk, work)) return 2;
+  *logdet = nf == 0.0 ? 0.0 : nf * std::log(shift) + (ldk - ldm);
+  return 0;
+}
+
+// For x = (B_FF + mu I)^-1 v_F = w 1_F o (v + R c), from p = R_F'v (S part first), vv = sum_F v_i^2, g_f and the factor
+// of K(mu): c (2col), *norm2 = x'x = w^2 (vv + 2 c'p + c'G_F c), *vx = v'x = w (vv + p'c) and *xbx =
+// x'(B_FF + mu I)^-1 x = w x'x + w t'c2 with t = R_F'x = w (p + G_F c) and c2 the coefficients of the solve on x (the
+// map applied, its matrix never formed); d(x'x) / d mu = -2 xbx.  work: 6 col doubles.  Returns qn_shift_coef's info.
+inline int qn_path_eval(int col, double theta, const double *kf, double w, const double *p, double vv,
+                        const double *g_f, double *c, double *norm2, double *vx, double *xbx, double *work) {
+  const int d = 2 * col;
+  double *t = work, *wt = work + d, *c2 = work + 2 * d;
+  for (int i = 0; i < d; ++i) wt[i] = w * p[i];
+  int info = qn_shift_coef(col, theta, kf, wt, wt + col, c, c + col);
+  if (info) return info;
+  double cp = 0.0, cgc = 0.0;
+  for (int i = 0; i < d; ++i) {
+    double gc = 0.0;
+    for (int j = 0; j < d; ++j) gc = gc + g_f[i + (size_t)j * d] * c[j];
+    t[i] = w * (p[i] + gc);
+    cp = cp + c[i] * p[i];
+    cgc = cgc + c[i] * gc;
+  }
+  *norm2 = w * w * ((vv + 2.0 * cp) + cgc);
+  *vx = w * (vv + cp);
+  for (int i = 0; i < d; ++i) wt[i] = w * t[i];
+  info = qn_shift_coef(col, theta, kf, wt, wt + col, c2, c2 + col);
+  if (info) return info;
+  double tc = 0.0;
+  for (int i = 0; i < d; ++i) tc = tc + t[i] * c2[i];
+  *xbx = w * *norm2 + w * tc;
+  return 0;
+}
+
+// The shift of a trust-region step: the mu >= 0 with ||x(mu)|| = delta, or 0 when ||x(0)|| <= delta, by Newton on
+// phi(mu) = 1 / ||x(mu)|| - 1 / delta (More and Sorensen) from mu = 0 inside a bracket [lo, hi], ||x(lo)|| > delta >=
+// ||x(hi)||: a Newton point outside the open bracket is replaced by its middle (by doubling while no upper end is
+// known).  eval(mu, &norm2, &xbx) evaluates x'x and x'(B + mu I)^-1 x and returns 0, or nonzero where the shifted
+// model is not positive definite (such a mu is a lower end).  Stops when | ||x|| - delta | <= rtol delta, when the
+// ends of the bracket are adjacent doubles (then at the upper end), or after max_it evaluations (then at the upper end
+// too, if one is known).  *mu, *norm2 and *xbx are those of the evaluation handed out, *iters the evaluations made.
+// Returns 0 (mu = 0 is inside), 1 (on the boundary to rtol), 2 (the adjacent-doubles exit), 3 (max_it reached: the
+// upper end, ||x|| <= delta but not to rtol), 4 (max_it reached with no upper end known: every evaluation had ||x|| >
+// delta, *mu is the last of them and NOT a step inside the region) or -1 (the model is not positive definite at
+// mu = 0 and no evaluation succeeded).  So 0 .. 3 always hand out ||x|| <= delta (1 + rtol).
+template <typename F>
+inline int qn_path_secular(double delta, double rtol, int max_it, F &&eval, double *mu, double *norm2, double *xbx,
+                           int *iters) {
+  double lo = 0.0, hi = HUGE_VAL, m = 0.0, n2 = 0.0, xb = 0.0;
+  double hi_n2 = 0.0, hi_xb = 0.0;
+  bool any = false;
+  int it = 0, rc = 3;
+  *mu = 0.0, *norm2 = 0.0, *xbx = 0.0;
+  while (it < max_it) {
+    const int info = eval(m, &n2, &xb);
+    ++it;
+    double next;
+    if (info == 0) {
+      const double nx = std::sqrt(n2);
+      any = true, *mu = m, *norm2 = n2, *xbx = xb;
+      if (m == 0.0 && nx <= delta) {
+        rc = 0;
+        break;
+      }
+      if (std::fabs(nx - delta) <= rtol * delta) {
+        rc = 1;
+        break;
+      }
+      if (nx > delta) lo = m;
+      else hi = m, hi_n2 = n2, hi_xb = xb;
+      next = m + (nx - delta) / delta * (n2 / xb);
+    } else {
+      lo = m;
+      next = HUGE_VAL;
+    }
+    if (hi < HUGE_VAL && !(std::nextafter(lo, hi) < hi)) {  // nothing between the ends
+      *mu = hi, *norm2 = hi_n2, *xbx = hi_xb;
+      rc = 2;
+      break;
+    }
+    if (!(next > lo && next < hi)) next = hi < HUGE_VAL ? lo + 0.5 * (hi - lo) : (lo > 0.0 ? 2.0 * lo : 1.0);
+    if (!(next > lo)) next = std::nextafter(lo, hi);
+    m = next;
+  }
+  *iters = it;
+  if (!any) return -1;
+  if (rc == 3) {  // max_it ran out: the upper end of the bracket where one is known, else nothing to hand out
+    if (!(hi < HUGE_VAL)) return 4;
+    *mu = hi, *norm2 = hi_n2, *xbx = hi_xb;
+  }
+  return rc;
+}
+
 // ---- entries at index lists (lbfgsb_hip_qn_block / qn_cols and the shifted twins) ----
 // The gathered rows of [S, Y] lie column by column: r[j + c ldr] is entry idx_j of logical column c (c < col: S, else
 // Y), j < k, as the gather delivers them.

@@ -636,6 +636,24 @@ hipError_t launch_qn_cols(const Queue &q, int64_t n, int64_t row0, WStore<T> w, 
                           bool acc, const double *coef, const double *dterm, const int64_t *idx, const double *wgt,
                           int k, T *out, int64_t ldo);
 
+// The model along a path of shifts (k_qn_path.hip, lbfgsb_hip_qn_path_*): one byte per row (1 = free) in place of the
+// weights of the passes above, the shifts being scalars of the host.
+constexpr int QN_PATH_MAXK = 64;  // LBFGSB_QN_PATH_MAXK
+// fre[i] = 0 where bit (status[i] + 1) of code_mask is set (status == NULL: every row free); res[0] = the pinned rows
+hipError_t launch_qn_path_pin(const Queue &q, int64_t n, const int8_t *status, int code_mask, uint8_t *fre,
+                              double *part, double *res);
+// launch_qn_wtv's plain pass on fre o v: k = 1 vector in natural order, with dd its squared norm over the free rows in
+// res[2 mc]; or vslot, k = 1, 2, 4 columns of W read at their slots (the masked Gram)
+template <typename T>
+hipError_t launch_qn_path_wtv(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, int k,
+                              QnVecs<T> v, bool vslot, bool dd, const uint8_t *fre, double *part, double *res);
+// out_j[i] (+)= fre_i ? a[j] (acc ? 0 : v_i) + a[j] ([S, Y](i, tile) coef[j * 2 mc ...]) : +0 for all j < k <=
+// QN_PATH_MAXK in one launch; coef (qn_basis_pack's layout) and a: DEVICE memory, read through uniform loads
+template <typename T>
+hipError_t launch_qn_path_expand(const Queue &q, int64_t n, WStore<T> w, int head, int col, int c0, int mc, bool acc,
+                                 const double *coef, const double *a, const T *v, const uint8_t *fre, int k, T *out,
+                                 int64_t ldo);
+
 // Draws of the model (k_qn_draw.hip): the two passes above with the vectors generated, never loaded -- z_k[i] is the
 // N(0, 1) deviate of (seed, row0 + i, s0 + k) (philox.hpp).  k = 1, 2 or 4 (qn_kmax) samples from s0; s0 even
 // unless k = 1.

@@ -1876,6 +1876,7 @@ class Solver final : public lbfgsb_hip_ctx {
 #include "solver_doors.inl"     // routine doors (active, errclb, cauchy, freev, formk, cmprlb, subsm, lnsrlb, matupd)
 #include "solver_qn.inl"        // the curvature model B, H = B^-1 as device operators (qn_apply, qn_diag)
 #include "solver_qn_idx.inl"    // its entries, sub-blocks and columns at index lists (qn_rows, qn_block, qn_cols)
+#include "solver_qn_path.inl"   // ... along a path of shifts: solves, log-determinants, trust steps (qn_path_*)
 #include "solver_qn_pairs.inl"  // its stored pairs read back, loaded and appended to (qn_pairs_get / _set / _push)
 #include "solver_kkt.inl"       // the active set, the multipliers and the projected gradient (kkt, kkt_list)
 };

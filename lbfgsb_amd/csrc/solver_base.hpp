@@ -189,6 +189,13 @@ struct lbfgsb_hip_ctx {
   virtual int qn_shift_block(int64_t ka, const int64_t *h_ia, int64_t kb, const int64_t *h_ib, double *h_a,
                              int64_t lda) = 0;
   virtual int qn_shift_cols(int64_t k, const int64_t *h_idx, void *out, int64_t ldo) = 0;
+  // the model along a path of shifts (solver_qn_path.inl, lbfgsb_hip_qn_path_*)
+  virtual int qn_path_set(const int8_t *status, int code_mask, int64_t *h_pinned) = 0;
+  virtual int qn_path_logdet(int64_t k, const double *h_mu, double *h_logdet, int32_t *h_info) = 0;
+  virtual int qn_path_solve(const void *v, int64_t k, const double *h_mu, void *out, int64_t ldo, double *h_norm2,
+                            double *h_vx) = 0;
+  virtual int qn_path_trust(const void *g, double delta, double rtol, int max_it, void *step, double *h_res,
+                            int32_t *h_iters) = 0;
   // the stored pairs as device data (solver_qn_pairs.inl, lbfgsb_hip_qn_pairs_get / _set / _push)
   virtual int qn_pairs_get(int32_t cap, int32_t *h_col, double *h_theta, void *s_out, int64_t lds, void *y_out,
                            int64_t ldy) = 0;

@@ -53,6 +53,8 @@
       public :: lbfgsb_qn_shift_set, lbfgsb_qn_shift_solve, lbfgsb_qn_shift_logdet, lbfgsb_qn_shift_diag
       public :: lbfgsb_qn_shift_sqrt, lbfgsb_qn_shift_draw, lbfgsb_qn_shift_draw_logpdf   ! its factor and draws
       public :: lbfgsb_qn_shift_quad, lbfgsb_qn_shift_logpdf                              ! ... and densities
+      public :: lbfgsb_qn_path_set, lbfgsb_qn_path_logdet, lbfgsb_qn_path_solve, lbfgsb_qn_path_trust  ! ... over a
+      integer,parameter,public :: LBFGSB_QN_PATH_MAXK = 64                                            ! range of shifts
       public :: lbfgsb_qn_rows, lbfgsb_qn_block, lbfgsb_qn_cols       ! entries of B, H at lists of global 0-based rows
       public :: lbfgsb_qn_shift_block, lbfgsb_qn_shift_cols           ! ... and of (B + mu I + diag(d))^-1
       public :: lbfgsb_qn_pairs_get, lbfgsb_qn_pairs_set, lbfgsb_qn_pairs_push  ! the stored pairs as device data
@@ -194,6 +196,39 @@
             real(c_double) :: logdet
             integer(c_int) :: rc
          end function lbfgsb_hip_qn_shift_logdet
+         function lbfgsb_hip_qn_path_set(ctx,status,code_mask,pinned) bind(C,name='lbfgsb_hip_qn_path_set') result(rc)
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr),value :: ctx, status
+            integer(c_int),value :: code_mask
+            integer(c_int64_t) :: pinned
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_path_set
+         function lbfgsb_hip_qn_path_logdet(ctx,k,mu,logdet,info) bind(C,name='lbfgsb_hip_qn_path_logdet') result(rc)
+            import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx
+            integer(c_int64_t),value :: k
+            real(c_double) :: mu(*), logdet(*)
+            integer(c_int32_t) :: info(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_path_logdet
+         function lbfgsb_hip_qn_path_solve(ctx,v,k,mu,out,ldo,norm2,vx) bind(C,name='lbfgsb_hip_qn_path_solve')    &
+            result(rc)
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, v, out
+            integer(c_int64_t),value :: k, ldo
+            real(c_double) :: mu(*), norm2(*), vx(*)
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_path_solve
+         function lbfgsb_hip_qn_path_trust(ctx,g,delta,rtol,max_it,step,res,iters)                                 &
+            bind(C,name='lbfgsb_hip_qn_path_trust') result(rc)
+            import :: c_int, c_int32_t, c_double, c_ptr
+            type(c_ptr),value :: ctx, g, step
+            real(c_double),value :: delta, rtol
+            integer(c_int),value :: max_it
+            real(c_double) :: res(4)
+            integer(c_int32_t) :: iters
+            integer(c_int) :: rc
+         end function lbfgsb_hip_qn_path_trust
          function lbfgsb_hip_qn_shift_diag(ctx,out) bind(C,name='lbfgsb_hip_qn_shift_diag') result(rc)
             import :: c_int, c_ptr
             type(c_ptr),value :: ctx, out
@@ -673,6 +708,65 @@
       integer,intent(out) :: rc
       rc = lbfgsb_hip_qn_shift_diag(ctx, out)
       end subroutine lbfgsb_qn_shift_diag
+
+      ! The model over a range of shifts (include/lbfgsb_hip.h, "The model over a range of shifts"): (B_FF + mu I)^-1 on
+      ! the rows F that are not pinned, for any number of shifts after one lbfgsb_qn_path_set.  status: a device buffer
+      ! of n int8 codes as lbfgsb_kkt writes them, or c_null_ptr (nothing pinned); bit (code + 1) of code_mask selects
+      ! a code to PIN (28 = 0b11100: at a lower bound, at an upper bound, fixed); pinned receives the pinned rows of all
+      ! ranks.  lbfgsb_qn_path_logdet: host only, logdet(j) = log det (B_FF + mu(j) I) where info(j) = 0 (1: theta +
+      ! mu <= 0 or not finite, 2: not positive definite).  lbfgsb_qn_path_solve: out + (j-1)*ldo = (B_FF + mu(j) I)^-1
+      ! v_F for k <= 64 shifts, norm2(j) = ||x_j||^2 and vx(j) = v'x_j; out may be c_null_ptr (the scalars alone).
+      ! lbfgsb_qn_path_trust: step = -(B_FF + mu I)^-1 g_F with ||step|| <= delta; res = (mu, ||step||, the predicted
+      ! decrease, on_boundary 0 / 1); rtol = 0 and max_it = 0 select 1e-10 and 100; step may be c_null_ptr.  After a
+      ! return that stores a pair the last three return LBFGSB_E_STATE until lbfgsb_qn_path_set is called again.
+      subroutine lbfgsb_qn_path_set(ctx, status, code_mask, pinned, rc)
+      type(c_ptr),intent(in) :: ctx, status
+      integer,intent(in) :: code_mask
+      integer(c_int64_t),intent(out) :: pinned
+      integer,intent(out) :: rc
+      pinned = 0
+      rc = lbfgsb_hip_qn_path_set(ctx, status, int(code_mask, c_int), pinned)
+      end subroutine lbfgsb_qn_path_set
+
+      subroutine lbfgsb_qn_path_logdet(ctx, k, mu, logdet, info, rc)
+      type(c_ptr),intent(in) :: ctx
+      integer,intent(in) :: k
+      real(c_double),intent(in) :: mu(k)
+      real(c_double),intent(out) :: logdet(k)
+      integer(c_int32_t),intent(out) :: info(k)
+      integer,intent(out) :: rc
+      real(c_double) :: mus(k)
+      mus = mu
+      logdet = 0.0_c_double
+      info = 0
+      rc = lbfgsb_hip_qn_path_logdet(ctx, int(k, c_int64_t), mus, logdet, info)
+      end subroutine lbfgsb_qn_path_logdet
+
+      subroutine lbfgsb_qn_path_solve(ctx, v, k, mu, out, ldo, norm2, vx, rc)
+      type(c_ptr),intent(in) :: ctx, v, out
+      integer,intent(in) :: k, ldo
+      real(c_double),intent(in) :: mu(k)
+      real(c_double),intent(out) :: norm2(k), vx(k)
+      integer,intent(out) :: rc
+      real(c_double) :: mus(k)
+      mus = mu
+      norm2 = 0.0_c_double
+      vx = 0.0_c_double
+      rc = lbfgsb_hip_qn_path_solve(ctx, v, int(k, c_int64_t), mus, out, int(ldo, c_int64_t), norm2, vx)
+      end subroutine lbfgsb_qn_path_solve
+
+      subroutine lbfgsb_qn_path_trust(ctx, g, delta, rtol, max_it, step, res, iters, rc)
+      type(c_ptr),intent(in) :: ctx, g, step
+      real(c_double),intent(in) :: delta, rtol
+      integer,intent(in) :: max_it
+      real(c_double),intent(out) :: res(4)
+      integer,intent(out) :: iters, rc
+      integer(c_int32_t) :: it
+      it = 0
+      res = 0.0_c_double
+      rc = lbfgsb_hip_qn_path_trust(ctx, g, delta, rtol, int(max_it, c_int), step, res, it)
+      iters = int(it)
+      end subroutine lbfgsb_qn_path_trust
 
       ! Square roots, draws and log-densities of the model plus a diagonal (include/lbfgsb_hip.h, "Square roots, draws
       ! and log-densities of the model plus a diagonal"): N(mean, scale^2 Sigma), Sigma = (B + mu I + D)^-1 on the free

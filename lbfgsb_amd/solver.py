@@ -594,6 +594,30 @@ class DeviceSolver:
                                                C.byref(pinned)))
         return QnShifted(self, int(pinned.value), float(mu))
 
+    def qn_path(self, status=None, codes=(1, 2, 3)) -> "QnPath":
+        """The model on the free rows over a range of shifts, (B_FF + mu I)^-1 for any number of mu, as a QnPath with
+        .pinned, .logdet(mus), .solve(v, mus) and .trust(g, delta).  status: an int8 CUDA tensor of n codes as kkt
+        writes them, or None (nothing pinned); codes: the status codes to PIN (default: the rows at a lower bound, at
+        an upper bound or fixed).  One pass makes the free bytes and counts the pinned rows, ceil(2 col / 4) masked
+        passes reduce the Gram of the pairs on the free rows (none without pins: the cached Gram); afterwards a new
+        shift costs the host a 2col x 2col factorisation and the device nothing.  Belongs to the pairs of this
+        return, as qn_shift's result; independent of it.  Collective on sharded contexts."""
+        import torch
+        mask = 0
+        if status is not None:
+            if not (isinstance(status, torch.Tensor) and status.is_cuda and status.dtype == torch.int8
+                    and status.dim() == 1 and status.numel() >= self.n and status.is_contiguous()):
+                raise TypeError("status must be a contiguous int8 CUDA tensor with n = %d rows" % self.n)
+            for c in ([codes] if isinstance(codes, (int, np.integer)) else codes):
+                if not -1 <= int(c) <= 3:
+                    raise ValueError("status codes are -1 .. 3")
+                mask |= 1 << (int(c) + 1)
+        pinned = C.c_int64(0)
+        self.wait_stream()
+        check(self.lib.lbfgsb_hip_qn_path_set(self.h, None if status is None else status.data_ptr(), mask,
+                                              C.byref(pinned)))
+        return QnPath(self, int(pinned.value))
+
     def qn_logpdf(self, x, mean=None, scale: float = 1.0, inverse: bool = True):
         """log N(x_j; mean, scale^2 A) over all rows of all ranks, the covariance A = H (inverse=True, as qn_draw's
         default) or B, for x of shape (n,) or (k, n): the quadratic form of A^-1 by qn_quad's pass and qn_logdet's
@@ -1149,6 +1173,103 @@ class QnShifted:
         return float(lp[0]) if x.dim() == 1 else lp
 
 
+class TrustStep:
+    """What QnPath.trust returns: step (an (n,) tensor, or None when it was not asked for), mu >= 0, norm = ||step||,
+    predicted = the decrease -(g's + s'Bs / 2) the model predicts, on_boundary (mu > 0: the constraint is active) and iters, the
+    host evaluations of the secular equation."""
+
+    def __init__(self, step, mu, norm, predicted, on_boundary, iters):
+        self.step, self.mu, self.norm, self.predicted = step, mu, norm, predicted
+        self.on_boundary, self.iters = on_boundary, iters
+
+    def __repr__(self):
+        return "TrustStep(mu=%r, norm=%r, predicted=%r, on_boundary=%r, iters=%r)" % (
+            self.mu, self.norm, self.predicted, self.on_boundary, self.iters)
+
+
+class QnPath:
+    """What DeviceSolver.qn_path returns: (B_FF + mu I)^-1 on the rows F that are not pinned, for the pairs of the
+    return it was made at and ANY shift mu: logdet, solve and trust take their shifts as host numbers.  `pinned` is the
+    number of pinned rows over all ranks.  The context holds one path: a later qn_path call replaces the free rows this
+    object works on, and a return that stores a pair makes every method raise LbfgsbError with the library's message."""
+
+    def __init__(self, solver: "DeviceSolver", pinned: int):
+        self.solver, self.pinned = solver, pinned
+
+    @staticmethod
+    def _mus(mus):
+        m = np.ascontiguousarray(np.atleast_1d(np.asarray(mus, np.float64)))
+        if m.ndim != 1 or m.size < 1:
+            raise ValueError("mus must be a scalar or a 1-d list of at least one shift")
+        return m
+
+    def logdet(self, mus):
+        """(logdet, info): log det (B_FF + mu_j I) for every shift of mus as a float64 array, NaN where info[j] != 0
+        (1: theta + mu_j <= 0 or not finite, 2: not positive definite on the free rows).  Host only: no launch."""
+        s = self.solver
+        m = self._mus(mus)
+        ld = np.full(m.size, np.nan)
+        info = np.zeros(m.size, np.int32)
+        check(s.lib.lbfgsb_hip_qn_path_logdet(s.h, int(m.size), m.ctypes.data_as(C.POINTER(C.c_double)),
+                                              ld.ctypes.data_as(C.POINTER(C.c_double)),
+                                              info.ctypes.data_as(C.POINTER(C.c_int32))))
+        return ld, info
+
+    def solve(self, v, mus, out=None, norms: bool = False):
+        """out[j] = (B_FF + mus[j] I)^-1 v_F for the (n,) tensor v and up to 64 shifts, as a (k, n) tensor; pinned rows
+        are +0.  One read pass, then one pass per 16 pairs that writes all k rows of out.  norms=True: returns
+        (out, norm2, vx) with the float64 arrays norm2[j] = ||out[j]||^2 and vx[j] = v'out[j] from the host formulas;
+        out=False with norms=True makes the read pass alone and returns (None, norm2, vx)."""
+        s = self.solver
+        v = s._qn_vec(v, "v")
+        if v.dim() != 1:
+            raise ValueError("v must have shape (n,)")
+        m = self._mus(mus)
+        k = int(m.size)
+        ldo = s.n
+        if out is False:
+            if not norms:
+                raise ValueError("out=False needs norms=True")
+            out = None
+        else:
+            out, ldo = s._qn_cols_out(k, out)
+        n2, vx = np.zeros(k), np.zeros(k)
+        dp = C.POINTER(C.c_double)
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_path_solve(s.h, v.data_ptr(), k, m.ctypes.data_as(dp),
+                                             None if out is None else out.data_ptr(), ldo,
+                                             n2.ctypes.data_as(dp) if norms else None,
+                                             vx.ctypes.data_as(dp) if norms else None))
+        s._qn_done()
+        return (out, n2, vx) if norms else out
+
+    def trust(self, g, delta: float, rtol: float = 0.0, max_it: int = 0, out=None) -> "TrustStep":
+        """The trust-region step of the model on the free rows: step = -(B_FF + mu I)^-1 g_F with mu >= 0, ||step|| <=
+        delta and mu (delta - ||step||) = 0 to rtol (0: 1e-10), by a safeguarded Newton iteration on the secular
+        equation that runs on the host.  out: an (n,) tensor for the step, None to allocate one, False for the
+        scalars alone.  Returns a TrustStep; its step is never outside the region (norm <= delta (1 + rtol)): if max_it evaluations do not get to
+        rtol it is the step at the upper end of the bracket (norm < delta), and if they find no shift with norm <= delta
+        at all the call raises LbfgsbError (LBFGSB_E_STATE) and writes nothing.  on_boundary says mu > 0."""
+        s = self.solver
+        g = s._qn_vec(g, "g")
+        if g.dim() != 1:
+            raise ValueError("g must have shape (n,)")
+        if out is False:
+            out = None
+        else:
+            out, _ = s._qn_cols_out(1, out)
+        res = np.zeros(4)
+        iters = C.c_int32(0)
+        s.wait_stream()
+        check(s.lib.lbfgsb_hip_qn_path_trust(s.h, g.data_ptr(), float(delta), float(rtol), int(max_it),
+                                             None if out is None else out.data_ptr(),
+                                             res.ctypes.data_as(C.POINTER(C.c_double)), C.byref(iters)))
+        s._qn_done()
+        if out is not None and out.dim() == 2:
+            out = out[0]
+        return TrustStep(out, float(res[0]), float(res[1]), float(res[2]), bool(res[3]), int(iters.value))
+
+
 class QnOperator:
     """The curvature model of a DeviceSolver's last return as a linear operator on this rank's rows: H = B^-1
     (inverse=True, what scipy's L-BFGS-B returns as hess_inv, but starting from the solver's theta) or B.
@@ -1183,6 +1304,11 @@ class QnOperator:
         """(B + mu I + diag(d))^-1 as a QnShifted (DeviceSolver.qn_shift): the shift is always added to B, whichever
         of B and H this operator is"""
         return self.solver.qn_shift(d=d, mu=mu)
+
+    def path(self, status=None, codes=(1, 2, 3)) -> "QnPath":
+        """(B_FF + mu I)^-1 on the rows that `status` and `codes` leave free, over any number of shifts, as a QnPath
+        (DeviceSolver.qn_path): the shifts are added to B, whichever of B and H this operator is"""
+        return self.solver.qn_path(status=status, codes=codes)
 
     def logdet(self) -> float:
         """log det A over all rows of all ranks (of a root: half of it)"""
